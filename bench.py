@@ -9,6 +9,9 @@ One step = the hot path over the whole batch, inputs resident in HBM:
 value = ICP edges aligned per second of whole-step wall time (all ranks, max over ranks).
 
 Usage: python bench.py [--gpus N --steps K --warmup W]   (torchrun sets RANK/WORLD_SIZE for N>1)
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds what takes
+runs of its own: the CPU baselines, the cold single solve and the caller's-order ICP runs.
+--dump-outputs DIR writes the last timed step's results as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -610,7 +613,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="config4")
     ap.add_argument("--cpu-sample", type=int, default=500, help="edges in the CPU-baseline ICP sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baselines out")
+    ap.add_argument("--full", action="store_true",
+                    help="batch workload: beside the headline also the CPU baselines (oracle ICP + GN on this host), "
+                         "the cold single solve on a fresh context and the caller's-order ICP runs; a plain run "
+                         "sets up, warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="batch workload: after the timed steps write what the last step computed (ICP results, "
+                         "covariance Hessians, GN poses) as DIR/<name>.npy")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend for N > 1 (nccl = RCCL over xGMI; gloo only to rehearse "
                          "the multi-rank path on fewer GPUs than ranks)")
@@ -756,16 +766,17 @@ def main():
             ctx.synchronize()
             cold["icp_kernel_ms_first_run"] = ctx.icp_kernel_ms()
     if args.schedule == "measured" and args.warmup > 0:
-        # the caller's order again, warm, beside the measured one (same results; untimed)
-        ctx.set_icp_schedule("caller")
-        ctx.icp_prepare(w.edges, w.est, params)
-        cms = []
-        for _ in range(3):
-            step()
-            ctx.synchronize()
-            cms.append(ctx.icp_kernel_ms())
-        cold["icp_kernel_ms_caller_order"] = float(np.median(cms))
-        ctx.set_icp_schedule("measured")
+        if args.full:
+            # the caller's order again, warm, beside the measured one (same results; untimed)
+            ctx.set_icp_schedule("caller")
+            ctx.icp_prepare(w.edges, w.est, params)
+            cms = []
+            for _ in range(3):
+                step()
+                ctx.synchronize()
+                cms.append(ctx.icp_kernel_ms())
+            cold["icp_kernel_ms_caller_order"] = float(np.median(cms))
+            ctx.set_icp_schedule("measured")
         ctx.icp_prepare(w.edges, w.est, params)   # every cost known: planned at once
         step()
     barrier()
@@ -803,9 +814,13 @@ def main():
     achieved = algo_bytes / (k_ms * 1e-3) / 1e9
     ck = sorted(cold)
     cold_red = dict(zip(ck, reduce([cold[k] for k in ck], dist.ReduceOp.MAX if world > 1 else None))) if ck else {}
-    res, _ = ctx.icp_fetch(with_hessian=False)   # a collective on the rank form
+    res, hess = ctx.icp_fetch(with_hessian=bool(args.dump_outputs))   # a collective on the rank form
+    if args.dump_outputs:
+        X = ctx.gn_get_poses(w.V)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, res, hess, X, st)
     cold_solve = None
-    if mode == "single":
+    if args.full and mode == "single":
         cold_solve = cold_single_solve(api, w, params, gp, gpu)
     stats = {"icp_kernel_ms": k_ms, "cov_kernel_ms": float(np.mean(cov_ms)), "index_build_ms": float(np.mean(idx_ms)),
              "gn_iterations": float(np.mean(gn_iters)), "gn_factorizations": float(np.mean(n_fact)),
@@ -813,7 +828,7 @@ def main():
              "icp_iters_mean": float(res["iterations"].mean()), "icp_iters_max": int(res["iterations"].max()),
              "final_error": st["final_error"], "pcg_iterations": st["pcg_iterations"], "gn_loop": "native"}
     cpu = None
-    if rank == 0 and mode == "single" and not args.no_cpu_baseline:
+    if args.full and rank == 0 and mode == "single" and not args.no_cpu_baseline:
         cores = host_cpus()
         cb = cpu_baseline(w, params, args.cpu_sample, threads=1)
         gnb = cpu_gn_baseline(w, res, params)
@@ -892,8 +907,8 @@ def main():
             **({"cold_single_solve_ms": cold_solve["total_ms"], "cold_single_solve": cold_solve} if cold_solve else {}),
             "cold_note": "icp_kernel_ms_first_run: the first warm-up step (no learnt costs: the caller's order, "
                          "the first launch after the upload); icp_kernel_ms_caller_order: the caller's order "
-                         "again after the warm-up (median of 3, untimed); icp_kernel_ms: the timed steps on the "
-                         "measured schedule (LPT + longest first from the warm-up's iteration counts)",
+                         "again after the warm-up (median of 3, untimed; with --full); icp_kernel_ms: the timed "
+                         "steps on the measured schedule (LPT + longest first from the warm-up's iteration counts)",
             "cov_kernel_ms": stats["cov_kernel_ms"],
             "cov_beside_gn": ctx.cov_overlapped(),
             "index_build_ms": stats["index_build_ms"],
@@ -925,6 +940,22 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     ctx.close()
+
+
+def dump_outputs(out_dir, res, hess, X, st):
+    """--dump-outputs: what the last timed step computed, as the step's caller receives it -- every
+    edge's ICP result record field by field, the covariance block's Hessians, the poses of the
+    Gauss-Newton solve and its closing numbers -- one <name>.npy each, float32 or float64 (about
+    3.1 MB at config 4, so nothing is sampled).  The workload is seeded: two builds run with the
+    same arguments can be compared file by file."""
+    os.makedirs(out_dir, exist_ok=True)
+    out = {"icp_T": res["T"].astype(np.float32), "icp_z": res["z"].astype(np.float32),
+           "icp_flags": np.stack([res[k] for k in ("converged", "iterations", "n_corr", "status")], 1).astype(np.float64),
+           "icp_fitness": res["fitness"].astype(np.float64), "icp_cov_hessian": np.asarray(hess, np.float64),
+           "gn_poses": np.asarray(X, np.float64),
+           "gn_stats": np.asarray([st["iterations"], st["final_error"]], np.float64)}
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def cold_single_solve(api, w, params, gp, gpu):

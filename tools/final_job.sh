@@ -15,10 +15,10 @@ timeout -k 10 500 python -u -m pytest tests -x -v -m gpu --timeout 200 --timeout
 rc=$?; echo "tests exit $rc"; tail -2 "$OUT/tests.log"; [ $rc -eq 0 ] || exit $rc
 timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1
 rc=$?; echo "smoke exit $rc"; tail -1 "$OUT/smoke.log"; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 400 python -u bench.py --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 400 python -u bench.py --full --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"
 rc=$?; echo "bench exit $rc"; cat "$OUT/bench.json"; [ $rc -eq 0 ] || exit $rc
 for cfg in config2 config3; do   # "batched ICP + single GN solve" configs: their step and one-off cost
-  timeout -k 10 300 python -u bench.py --config $cfg --steps 10 --warmup 3 > "$OUT/bench_$cfg.json" 2> "$OUT/bench_$cfg.err"
+  timeout -k 10 300 python -u bench.py --full --config $cfg --steps 10 --warmup 3 > "$OUT/bench_$cfg.json" 2> "$OUT/bench_$cfg.err"
   rc=$?; echo "bench $cfg exit $rc"; [ $rc -eq 0 ] || exit $rc
 done
 timeout -k 10 300 python -u bench.py --workload incremental > "$OUT/inc.json" 2> "$OUT/inc.err"
