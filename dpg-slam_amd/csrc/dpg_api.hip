@@ -158,6 +158,10 @@ struct dpg_ctx {
     bool gn_ready = false;
     dpg_gn_params gp{};
     float asm_ms = 0.f, solve_ms = 0.f;
+    // node pairs (lo << 32 | hi, sorted) that share a factor of the graph set up: built from the
+    // device's factor list by the first dpg_gn_marginal_pairs after a setup
+    std::vector<uint64_t> gn_pairs;
+    bool gn_pairs_valid = false;
     // the pipelined GN loop (dpg_gn_pipe.h): control block, two host-mapped report slots + events
     dpg_gn_ctl* pipe_ctl = nullptr;
     dpg_gn_slot* pipe_slot = nullptr;
@@ -1502,6 +1506,7 @@ static int gn_setup_1(dpg_ctx* c, int64_t V, const dpg_factor* F, int64_t nf, in
     if (c->gn_ready) dpg_gn_dev_free(&c->gn);
     c->gn = ng;
     c->gn_ready = true;
+    c->gn_pairs_valid = false;
     if (gp) c->gp = *gp;
     else dpg_gn_params_default(&c->gp);
     return DPG_OK;
@@ -2084,6 +2089,132 @@ int dpg_optimize_graph(dpg_ctx* c, double* poses, int64_t V, const dpg_factor* F
     if (rc) return rc;
     if ((rc = dpg_gn_set_poses(c, poses))) return rc;
     return gn_loop(c, P, poses, t0, now_ms(), st);
+}
+
+// ---- marginal covariances (gtsam::Marginals, dpg_slam_main.cc:272-279) ----
+// The graph of the last setup is linearized at its current poses and factored (a chord step may
+// have left the factor of an earlier iterate; Marginals linearizes at the values it is given),
+// then the selected inverse of that factor gives the blocks (dpg_chol.hip).  The loop's state is
+// left alone: poses, step sizes, the factorization count and whether it holds a factor at all
+// (after dpg_gn_set_poses it does not, and its first solve factors as it would have anyway; a
+// factor it did hold is replaced by the one at the current poses).
+static int gn_marginals_state(dpg_ctx* c, const char* fn) {
+    if (!c || !c->gn_ready) return fail(DPG_ERR_STATE, "%s: graph not set up", fn);
+    if (is_multi(c)) return fail(DPG_ERR_STATE, "%s: marginals are single-device (this context has several ranks)", fn);
+    if (c->gp.linear_solver != DPG_SOLVER_CHOLESKY || !c->gn.chol)
+        return fail(DPG_ERR_STATE, "%s: the graph has no Cholesky factorization (linear_solver)", fn);
+    return DPG_OK;
+}
+
+static int gn_marginals_blocks(dpg_ctx* c, const char* fn, const int32_t* nodes, int64_t n, const int32_t* pairs,
+                               int64_t n_pairs, double* out, double* ms) {
+    int rc = gn_marginals_state(c, fn);
+    if (rc) return rc;
+    if (!out || n < 0 || n_pairs < 0) return fail(DPG_ERR_ARG, "%s: bad arguments", fn);
+    if (dpg_chol_selinv_check(c->gn.chol, nodes, n, pairs, n_pairs))
+        return fail(DPG_ERR_ARG, "%s: a node is out of range or a pair's block is outside the factor's pattern", fn);
+    HIP_TRY(hipSetDevice(c->device));
+    dpg_gn_dev* g = &c->gn;
+    const bool timed = ms != nullptr;
+    if (timed) HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+    if ((rc = dpg_gn_dev_assemble(g, g->hb_own, c->stream))) return fail(rc, "%s: assembly launch failed", fn);
+    if (timed) HIP_TRY(hipEventRecord(c->ev[4], c->stream));
+    if ((rc = dpg_chol_solve(g->chol, g->hb_own, c->stream))) return fail(rc, "%s: factorization launch failed", fn);
+    if (timed) HIP_TRY(hipEventRecord(c->ev[5], c->stream));
+    rc = dpg_chol_marginals(g->chol, nodes, n, pairs, n_pairs, out, c->stream);
+    if (rc == DPG_ERR_NUMERIC) return fail(rc, "%s: H is not positive definite", fn);
+    if (rc) return fail(rc, "%s: selected inversion failed", fn);
+    if (timed) {
+        float a = 0.f, f = 0.f;
+        HIP_TRY(hipEventElapsedTime(&a, c->ev[3], c->ev[4]));
+        HIP_TRY(hipEventElapsedTime(&f, c->ev[4], c->ev[5]));
+        ms[0] = a;
+        ms[1] = f;
+    }
+    return DPG_OK;
+}
+
+int dpg_gn_marginals(dpg_ctx* c, const int32_t* nodes, int64_t n, double* cov_out) {
+    if (c && c->gn_ready && !nodes && n != c->gn.n_nodes)
+        return fail(DPG_ERR_ARG, "dpg_gn_marginals: nodes == NULL asks for every node (n = %lld)", (long long)c->gn.n_nodes);
+    return gn_marginals_blocks(c, "dpg_gn_marginals", nodes, n, nullptr, 0, cov_out, nullptr);
+}
+
+// the pairs must share a factor (H's own pattern): blocks that only fill or a relaxed supernode put
+// into L's pattern are not part of the interface
+static int gn_pairs_share_factor(dpg_ctx* c, const int32_t* pairs, int64_t n) {
+    const dpg_gn_dev& g = c->gn;
+    if (!c->gn_pairs_valid) {
+        HIP_TRY(hipSetDevice(c->device));
+        std::vector<dpg_factor> F((size_t)g.n_factors);
+        if (g.n_factors > 0) {
+            HIP_TRY(hipMemcpyAsync(F.data(), g.factors, sizeof(dpg_factor) * F.size(), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+        }
+        c->gn_pairs.clear();
+        for (const dpg_factor& f : F)
+            if (f.kind == DPG_FACTOR_BETWEEN && f.i != f.j)
+                c->gn_pairs.push_back((uint64_t)(uint32_t)std::min(f.i, f.j) << 32 | (uint32_t)std::max(f.i, f.j));
+        std::sort(c->gn_pairs.begin(), c->gn_pairs.end());
+        c->gn_pairs.erase(std::unique(c->gn_pairs.begin(), c->gn_pairs.end()), c->gn_pairs.end());
+        c->gn_pairs_valid = true;
+    }
+    for (int64_t q = 0; q < n; ++q) {
+        const int32_t i = pairs[2 * q], j = pairs[2 * q + 1];
+        if (i < 0 || j < 0 || i >= g.n_nodes || j >= g.n_nodes)
+            return fail(DPG_ERR_ARG, "dpg_gn_marginal_pairs: pair %lld has a node out of range", (long long)q);
+        if (i != j && !std::binary_search(c->gn_pairs.begin(), c->gn_pairs.end(),
+                                          (uint64_t)(uint32_t)std::min(i, j) << 32 | (uint32_t)std::max(i, j)))
+            return fail(DPG_ERR_ARG, "dpg_gn_marginal_pairs: nodes %d and %d share no factor", i, j);
+    }
+    return DPG_OK;
+}
+
+int dpg_gn_marginal_pairs(dpg_ctx* c, const int32_t* pairs, int64_t n, double* cov_out) {
+    if (n > 0 && !pairs) return fail(DPG_ERR_ARG, "dpg_gn_marginal_pairs: pairs is NULL");
+    int rc = gn_marginals_state(c, "dpg_gn_marginal_pairs");
+    if (rc) return rc;
+    if (n < 0 || !cov_out) return fail(DPG_ERR_ARG, "dpg_gn_marginal_pairs: bad arguments");
+    if ((rc = gn_pairs_share_factor(c, pairs, n))) return rc;
+    return gn_marginals_blocks(c, "dpg_gn_marginal_pairs", nullptr, 0, pairs, n, cov_out, nullptr);
+}
+
+int dpg_marginal_covariances(dpg_ctx* c, const double* poses, int64_t V, const dpg_factor* F, int64_t nf,
+                             const int32_t* nodes, int64_t n, double* cov_out) {
+    if (!c || !F || !poses || !cov_out || V <= 0 || nf < 0 || n < 0 || (!nodes && n != V))
+        return fail(DPG_ERR_ARG, "dpg_marginal_covariances: bad arguments");
+    if (is_multi(c)) return fail(DPG_ERR_STATE, "dpg_marginal_covariances: marginals are single-device");
+    for (int64_t q = 0; nodes && q < n; ++q)
+        if (nodes[q] < 0 || nodes[q] >= V) return fail(DPG_ERR_ARG, "dpg_marginal_covariances: node %lld out of range", (long long)q);
+    int rc = dpg_gn_setup(c, V, F, nf, 0, nf, nullptr);
+    if (rc) return rc;
+    if ((rc = dpg_gn_set_poses(c, poses))) return rc;
+    return dpg_gn_marginals(c, nodes, n, cov_out);
+}
+
+/* Diagnostic (tools/marginals_probe.py): dpg_gn_marginals of every node with its parts timed by HIP
+ * events.  out = {assembly ms, factorization + solve ms, levels, Sigma + work buffer bytes, then the
+ * selected inversion's launches, roots' level first}; returns the number of values written. */
+int64_t dpg_gn_marginals_profile(dpg_ctx* c, double* out, int64_t cap) {
+    int rc = gn_marginals_state(c, "dpg_gn_marginals_profile");
+    if (rc) return rc;
+    if (!out || cap < 4) return fail(DPG_ERR_ARG, "dpg_gn_marginals_profile: bad arguments");
+    std::vector<double> cov((size_t)(9 * c->gn.n_nodes));
+    double ms[2];
+    if ((rc = gn_marginals_blocks(c, "dpg_gn_marginals_profile", nullptr, c->gn.n_nodes, nullptr, 0, cov.data(), ms)))
+        return rc;
+    double st[6];
+    dpg_chol_stats(c->gn.chol, st);
+    const int nl = (int)st[1];
+    std::vector<float> lv((size_t)nl, 0.f);
+    if ((rc = dpg_chol_selinv_timed(c->gn.chol, c->stream, lv.data(), nl))) return fail(rc, "selected inversion failed");
+    out[0] = ms[0];
+    out[1] = ms[1];
+    out[2] = nl;
+    out[3] = (double)dpg_chol_selinv_bytes(c->gn.chol);
+    int64_t k = 4;
+    for (int q = 0; q < nl && k < cap; ++q) out[k++] = lv[(size_t)q];
+    return k;
 }
 
 // ---- re-linearisation sweep (DpgSLAM::reoptimize) ----

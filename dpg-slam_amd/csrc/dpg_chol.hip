@@ -1998,6 +1998,162 @@ __global__ __launch_bounds__(256) void chol_copy_runs(const double* __restrict__
         dst[d0 + i] = src[s0 + i];
 }
 
+// ---- selected inverse: the blocks of Sigma = H^-1 inside L's pattern (marginal covariances) ----
+// Takahashi's recurrence in multifrontal form, one root-to-leaves pass over the supernodal tree.
+// Front s has pivot columns C (k3 scalars) and rows R (r3); with Y = L21 L11^-1 and Z = L11^-1
+//   G        = Sigma_parent(relmap(R), relmap(R))        (R lies inside the parent's index set)
+//   Sigma_RC = -G Y
+//   Sigma_CC = Z^T Z - Y^T Sigma_RC
+// and the front's whole (k3 + r3)^2 block [[Sigma_CC, Sigma_RC^T], [Sigma_RC, G]] goes to the Sigma
+// buffer (the fronts' layout, full symmetric storage), so a child gathers from its parent alone.
+// One launch per elimination-tree level from the roots' down, one workgroup per front: a front's
+// parent lies on a higher level, so stream order is the only synchronisation.  No atomics; every
+// element is one thread's sum in a fixed order (four accumulators: a dependent fp64 chain costs
+// ~32 cycles a step on one wave), so two runs on one factor are bitwise equal.
+//   rows:  [Z; Y] = [I; L21] L11^-1, one row per thread by substitution from the right;
+//   G Y:   one element per thread, G's column contiguous across the threads;
+//   Sigma_CC: lower triangle, one element per thread, mirrored by the same thread.
+// A front whose L11, [Z; Y] and Sigma block fit kSelLds doubles (60 KiB, 63 KiB with the table of
+// diagonal reciprocals: two workgroups per CU of 160 KiB; 15 block rows always fit, up to 28 with few
+// pivot columns) works in LDS (leading dimensions padded to odd) and stores its block once; a larger one (up to
+// 381 rows) works in HBM: Sigma in place, [Z; Y] in the work buffer.
+constexpr int kSelLds = 7680;
+__host__ __device__ inline int sel_pad(int m3) { return m3 | 1; }
+__host__ __device__ inline int sel_lds_doubles(int m3, int k3) { return k3 * k3 + sel_pad(m3) * (k3 + m3); }
+
+__global__ __launch_bounds__(kT) void chol_selinv_level(const int32_t* __restrict__ list, const SnDev* __restrict__ sns,
+                                                        const int32_t* __restrict__ relmap,
+                                                        const int64_t* __restrict__ woff,
+                                                        const double* __restrict__ fronts, double* sel, double* work) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    __shared__ double s_rd[384];   // 1 / L(j, j) (k3 <= 381)
+    const int tid = threadIdx.x;
+    const int32_t s = list[blockIdx.x];
+    const SnDev S = sns[s];
+    const int k3 = 3 * S.k, r3 = 3 * S.r, m3 = k3 + r3;
+    const bool lds = sel_lds_doubles(m3, k3) <= kSelLds;
+    const double* F = fronts + S.front_off;
+    double* Sg = sel + S.front_off;
+    // L11 (leading dimension ll), X = [Z; Y] (m3 x k3, lx), the Sigma block (m3 x m3, lw)
+    const double* L11 = F;
+    double* X = work + woff[s];
+    double* W = Sg;
+    int ll = m3, lx = m3, lw = m3;
+    if (lds) {
+        double* l11 = sm;
+        ll = k3;
+        lx = lw = sel_pad(m3);
+        X = sm + k3 * k3;
+        W = X + lx * k3;
+        for (int e = tid; e < k3 * k3; e += kT) {
+            const int i = e % k3, j = e / k3;
+            l11[e] = i >= j ? F[(int64_t)j * m3 + i] : 0.0;
+        }
+        L11 = l11;
+    }
+    for (int j = tid; j < k3; j += kT) s_rd[j] = 1.0 / F[(int64_t)j * m3 + j];
+    // G from the parent's finished block
+    if (r3 > 0) {
+        const SnDev Pn = sns[S.parent];
+        const int mp3 = 3 * (Pn.k + Pn.r);
+        const double* P = sel + Pn.front_off;
+        const int32_t* rm = relmap + S.rows_off;
+        for (int e = tid; e < r3 * r3; e += kT) {
+            const int a = e % r3, b = e / r3;
+            const int pa = 3 * rm[a / 3] + a % 3, pb = 3 * rm[b / 3] + b % 3;
+            W[(int64_t)(k3 + b) * lw + k3 + a] = P[(int64_t)pb * mp3 + pa];
+        }
+    }
+    __syncthreads();
+    // rows of [Z; Y]: x L11 = (e_i | L21(i, :)), columns from the right
+    for (int i = tid; i < m3; i += kT) {
+        const int jt = i < k3 ? i : k3 - 1;
+        for (int j = k3 - 1; j > jt; --j) X[(int64_t)j * lx + i] = 0.0;
+        for (int j = jt; j >= 0; --j) {
+            const double b = i < k3 ? (j == i ? 1.0 : 0.0) : F[(int64_t)j * m3 + i];
+            const double* lc = L11 + (int64_t)j * ll;
+            double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+            int c = j + 1;
+            for (; c + 3 <= jt; c += 4) {
+                a0 = fma(X[(int64_t)c * lx + i], lc[c], a0);
+                a1 = fma(X[(int64_t)(c + 1) * lx + i], lc[c + 1], a1);
+                a2 = fma(X[(int64_t)(c + 2) * lx + i], lc[c + 2], a2);
+                a3 = fma(X[(int64_t)(c + 3) * lx + i], lc[c + 3], a3);
+            }
+            for (; c <= jt; ++c) a0 = fma(X[(int64_t)c * lx + i], lc[c], a0);
+            X[(int64_t)j * lx + i] = (b - ((a0 + a1) + (a2 + a3))) * s_rd[j];
+        }
+    }
+    __syncthreads();
+    // Sigma_RC = -G Y, and its transpose
+    for (int e = tid; e < r3 * k3; e += kT) {
+        const int i = e % r3, c = e / r3;
+        const double* gi = W + (int64_t)k3 * lw + k3 + i;      // G(i, j) at gi[j * lw]
+        const double* yc = X + (int64_t)c * lx + k3;            // Y(j, c) at yc[j]
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+        int j = 0;
+        for (; j + 3 < r3; j += 4) {
+            a0 = fma(gi[(int64_t)j * lw], yc[j], a0);
+            a1 = fma(gi[(int64_t)(j + 1) * lw], yc[j + 1], a1);
+            a2 = fma(gi[(int64_t)(j + 2) * lw], yc[j + 2], a2);
+            a3 = fma(gi[(int64_t)(j + 3) * lw], yc[j + 3], a3);
+        }
+        for (; j < r3; ++j) a0 = fma(gi[(int64_t)j * lw], yc[j], a0);
+        const double v = -((a0 + a1) + (a2 + a3));
+        W[(int64_t)c * lw + k3 + i] = v;
+        W[(int64_t)(k3 + i) * lw + c] = v;
+    }
+    __syncthreads();
+    // Sigma_CC(a, b), a >= b: sum_{c >= a} Z(c, a) Z(c, b) - sum_i Y(i, a) Sigma_RC(i, b)
+    for (int e = tid; e < k3 * k3; e += kT) {
+        const int a = e % k3, b = e / k3;
+        if (a < b) continue;
+        const double* xa = X + (int64_t)a * lx;
+        const double* xb = X + (int64_t)b * lx;
+        const double* wb = W + (int64_t)b * lw;
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+        int c = a;
+        for (; c + 3 < k3; c += 4) {
+            a0 = fma(xa[c], xb[c], a0);
+            a1 = fma(xa[c + 1], xb[c + 1], a1);
+            a2 = fma(xa[c + 2], xb[c + 2], a2);
+            a3 = fma(xa[c + 3], xb[c + 3], a3);
+        }
+        for (; c < k3; ++c) a0 = fma(xa[c], xb[c], a0);
+        double b0 = 0.0, b1 = 0.0, b2 = 0.0, b3 = 0.0;
+        c = k3;
+        for (; c + 3 < m3; c += 4) {
+            b0 = fma(xa[c], wb[c], b0);
+            b1 = fma(xa[c + 1], wb[c + 1], b1);
+            b2 = fma(xa[c + 2], wb[c + 2], b2);
+            b3 = fma(xa[c + 3], wb[c + 3], b3);
+        }
+        for (; c < m3; ++c) b0 = fma(xa[c], wb[c], b0);
+        const double v = ((a0 + a1) + (a2 + a3)) - ((b0 + b1) + (b2 + b3));
+        W[(int64_t)b * lw + a] = v;
+        W[(int64_t)a * lw + b] = v;
+    }
+    if (lds) {
+        __syncthreads();
+        for (int e = tid; e < m3 * m3; e += kT) {
+            const int i = e % m3, j = e / m3;
+            Sg[e] = W[j * lw + i];
+        }
+    }
+}
+
+// the requested 3x3 blocks out of the Sigma buffer, row-major: block q is at off (its (0, 0)
+// element) with leading dimension ld
+struct SelPick { int64_t off; int32_t ld, pad; };
+__global__ __launch_bounds__(256) void chol_selinv_pick(const SelPick* __restrict__ picks, int64_t n,
+                                                        const double* __restrict__ sel, double* __restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= 9 * n) return;
+    const SelPick p = picks[e / 9];
+    const int ii = (int)(e % 9) / 3, jj = (int)(e % 3);
+    out[e] = sel[p.off + (int64_t)jj * p.ld + ii];
+}
+
 // device buffers are kept between rebuilds of the same solver (an incremental graph re-derives its
 // structures every update): a buffer is re-allocated only when it must grow (by 1.5x at least)
 template <typename T>
@@ -2103,6 +2259,21 @@ struct CholDev {
     int64_t pstats[4] = {0, 0, 0, 0};   // last solve: fronts refactored, kept, doubles moved, host ns of the pick
     void* host = nullptr;         // CholHost of the build in progress (a plan and its upload may run
                                   // on different threads, one after the other)
+    // selected inverse (dpg_chol_selinv): nothing here is allocated or built before the first
+    // request.  `sel` has the fronts' layout; `sel_work` holds [Z; Y] of the fronts too large for
+    // LDS (sel_woff); sel_list = level_list on the device.  The lists belong to the analysis
+    // uploaded as number build_gen (sel_gen: the one they were built for).
+    bool has_factor = false;      // `fronts` holds a factorization under the current analysis
+    int64_t build_gen = 0, sel_gen = -1;
+    double* sel = nullptr;
+    double* sel_work = nullptr;
+    double* sel_out = nullptr;
+    char* sel_lists = nullptr;    // [int64 woff[ns] | int32 list[ns]]
+    SelPick* sel_picks = nullptr;
+    size_t c_sel = 0, c_sel_work = 0, c_sel_out = 0, c_sel_lists = 0, c_sel_picks = 0;
+    std::vector<size_t> sel_lds;  // per level: dynamic LDS bytes of its launch
+    std::vector<SelPick> h_picks;
+    std::vector<hipEvent_t> sel_ev;
 };
 
 void free_host(void* p);
@@ -2110,6 +2281,7 @@ void free_host(void* p);
 // a new analysis in; *S gets back one whose buffers the caller reuses.  With tracking, the analysis
 // of the last factorization moves to fac_sym instead (the partial refactorization compares with it)
 void take_sym(CholDev* c, dpg_chol_sym* S) {
+    c->has_factor = false;   // (the values in fronts belong to the analysis leaving)
     if (c->track && c->sym_is_fac) {
         std::swap(c->fac_sym, c->sym);
         c->fac_G.swap(c->cur_G);
@@ -2125,7 +2297,9 @@ extern "C" void dpg_chol_destroy(void* h) {
     if (!c) return;
     // (the structure arrays live in c->arena)
     if (c->aux) (void)hipStreamSynchronize(c->aux);
-    void* ptrs[] = {c->arena, c->fronts, c->acc, c->ysol, c->xsol, c->status, c->sync, c->dinv, c->linv, c->scratch, c->dpart};
+    void* ptrs[] = {c->arena, c->fronts, c->acc, c->ysol, c->xsol, c->status, c->sync, c->dinv, c->linv, c->scratch, c->dpart,
+                    c->sel, c->sel_work, c->sel_out, c->sel_lists, c->sel_picks};
+    for (hipEvent_t e : c->sel_ev) (void)hipEventDestroy(e);
     if (c->pev) (void)hipEventDestroy(c->pev);
     if (c->pstage) (void)hipHostFree(c->pstage);
     for (void* p : ptrs)
@@ -2723,6 +2897,8 @@ int chol_plan(CholDev* c, int64_t n, const int32_t* pair_lo, const int32_t* pair
 // copy into one device arena (the pointers of c point into it); one synchronisation at the end.
 int chol_upload(CholDev* c, int64_t n, const CholHost& H) {
     const dpg_chol_sym& S = c->sym;
+    ++c->build_gen;   // (the selected inverse's lists follow the analysis: rebuilt on its next request)
+    c->has_factor = false;
     auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
     struct Piece { void** d; const void* h; size_t bytes; };
     Piece pieces[24];
@@ -2899,6 +3075,7 @@ static void note_factored(CholDev* c, int64_t refactored, int64_t kept, int64_t 
     c->pstats[1] = kept;
     c->pstats[2] = moved;
     c->pstats[3] = pick_ns;
+    c->has_factor = true;
     if (!c->track) return;
     c->fac_valid = true;
     c->fac_ptr = c->fronts;
@@ -2972,7 +3149,9 @@ extern "C" void dpg_chol_track_factor(void* h, int on) {
     c->cur_G.clear();   // the current analysis was planned untracked: its team sizes are unknown
 }
 extern "C" void dpg_chol_forget_factor(void* h) {
-    if (h) reinterpret_cast<CholDev*>(h)->fac_valid = false;
+    if (!h) return;
+    reinterpret_cast<CholDev*>(h)->fac_valid = false;
+    reinterpret_cast<CholDev*>(h)->has_factor = false;
 }
 extern "C" void dpg_chol_partial_stats(void* h, int64_t out[4]) {
     const CholDev* c = reinterpret_cast<const CholDev*>(h);
@@ -3173,6 +3352,7 @@ extern "C" int dpg_chol_solve_gated(void* h, const double* hb, const int32_t* ga
     CholDev* c = reinterpret_cast<CholDev*>(h);
     if (!dpg_chol_gated_ok(h)) return DPG_ERR_STATE;
     c->fac_valid = false;   // (a Gauss-Newton loop's refactorizations are not tracked)
+    c->has_factor = true;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const dpg_chol_sym& S = c->sym;
     const double* g = hb + 9 * c->nnzb_upper;
@@ -3236,6 +3416,183 @@ extern "C" void dpg_chol_stats(void* h, double out[6]) {
     out[3] = S.flops;
     out[4] = (double)S.front_off[(size_t)S.ns] * 8.0;
     out[5] = (double)S.n;
+}
+
+// ---- selected inverse: host side ----
+namespace {
+// the Sigma buffer, the work buffer and the lists of the current analysis (once per analysis)
+int selinv_prepare(CholDev* c, hipStream_t st) {
+    const dpg_chol_sym& S = c->sym;
+    const size_t total = (size_t)S.front_off[(size_t)S.ns];
+    if (c->sel_gen == c->build_gen && c->sel && total <= c->c_sel) return DPG_OK;
+    // (an earlier request's kernels may still read what is rebuilt here)
+    if (hipStreamSynchronize(st) != hipSuccess) return DPG_ERR_HIP;
+    const int32_t ns = S.ns;
+    std::vector<int64_t> woff((size_t)ns);
+    c->sel_lds.assign((size_t)S.n_levels, 0);
+    int64_t wtot = 0;
+    for (int32_t s = 0; s < ns; ++s) {
+        const int k3 = 3 * (S.sn_c0[(size_t)s + 1] - S.sn_c0[(size_t)s]);
+        const int m3 = k3 + 3 * (int)(S.sn_rows_ptr[(size_t)s + 1] - S.sn_rows_ptr[(size_t)s]);
+        if (k3 > 384) return DPG_ERR_SIZE;   // (the kernel's table of diagonal reciprocals)
+        woff[(size_t)s] = wtot;
+        const int need = sel_lds_doubles(m3, k3);
+        if (need <= kSelLds) {
+            size_t& l = c->sel_lds[(size_t)S.sn_level[(size_t)s]];
+            l = std::max(l, sizeof(double) * (size_t)need);
+        } else {
+            wtot += (int64_t)m3 * k3;
+        }
+    }
+    const size_t lb = sizeof(int64_t) * (size_t)ns + sizeof(int32_t) * (size_t)ns;
+    if (dreserve(&c->sel, &c->c_sel, total) || dreserve(&c->sel_work, &c->c_sel_work, (size_t)wtot) ||
+        dreserve(&c->sel_lists, &c->c_sel_lists, lb))
+        return DPG_ERR_HIP;
+    if (hipMemcpy(c->sel_lists, woff.data(), sizeof(int64_t) * (size_t)ns, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(c->sel_lists + sizeof(int64_t) * (size_t)ns, S.level_list.data(), sizeof(int32_t) * (size_t)ns,
+                  hipMemcpyHostToDevice) != hipSuccess)
+        return DPG_ERR_HIP;
+    c->sel_gen = c->build_gen;
+    return DPG_OK;
+}
+
+// level_ms (may be NULL): the time of each level's launch, roots' level first, from HIP events
+int selinv_run(CholDev* c, hipStream_t st, float* level_ms, int cap) {
+    if (!c || !c->has_factor) return DPG_ERR_STATE;
+    const int rc = selinv_prepare(c, st);
+    if (rc) return rc;
+    const dpg_chol_sym& S = c->sym;
+    const int64_t* woff = reinterpret_cast<const int64_t*>(c->sel_lists);
+    const int32_t* list = reinterpret_cast<const int32_t*>(c->sel_lists + sizeof(int64_t) * (size_t)S.ns);
+    const bool timed = level_ms != nullptr;
+    if (timed) {
+        while ((int32_t)c->sel_ev.size() < S.n_levels + 1) {
+            hipEvent_t e;
+            if (hipEventCreate(&e) != hipSuccess) return DPG_ERR_HIP;
+            c->sel_ev.push_back(e);
+        }
+        if (hipEventRecord(c->sel_ev[0], st) != hipSuccess) return DPG_ERR_HIP;
+    }
+    for (int32_t l = S.n_levels - 1, q = 1; l >= 0; --l, ++q) {
+        const int32_t b = S.level_ptr[(size_t)l], n = S.level_ptr[(size_t)l + 1] - b;
+        if (n > 0)
+            hipLaunchKernelGGL(chol_selinv_level, dim3((unsigned)n), dim3(kT), c->sel_lds[(size_t)l], st, list + b, c->sns,
+                               c->relmap, woff, c->fronts, c->sel, c->sel_work);
+        if (timed && hipEventRecord(c->sel_ev[(size_t)q], st) != hipSuccess) return DPG_ERR_HIP;
+    }
+    if (hipGetLastError() != hipSuccess) return DPG_ERR_HIP;
+    if (timed) {
+        if (hipEventSynchronize(c->sel_ev[(size_t)S.n_levels]) != hipSuccess) return DPG_ERR_HIP;
+        for (int32_t q = 0; q < S.n_levels && q < cap; ++q)
+            if (hipEventElapsedTime(level_ms + q, c->sel_ev[(size_t)q], c->sel_ev[(size_t)q + 1]) != hipSuccess)
+                return DPG_ERR_HIP;
+    }
+    return DPG_OK;
+}
+
+// block (row node i, column node j) of Sigma in the front of the earlier of the two; false when
+// the block is outside L's pattern
+bool sel_locate(const dpg_chol_sym& S, int32_t i, int32_t j, SelPick* p) {
+    const int32_t pi = S.pos[(size_t)i], pj = S.pos[(size_t)j];
+    const int32_t s = S.sn_of[(size_t)std::min(pi, pj)];
+    const int32_t c0 = S.sn_c0[(size_t)s], k = S.sn_c0[(size_t)s + 1] - c0;
+    const int32_t* rb = S.sn_rows.data() + S.sn_rows_ptr[(size_t)s];
+    const int32_t r = (int32_t)(S.sn_rows_ptr[(size_t)s + 1] - S.sn_rows_ptr[(size_t)s]);
+    auto local = [&](int32_t q) -> int32_t {
+        if (q < c0 + k) return q - c0;
+        const int32_t* it = std::lower_bound(rb, rb + r, q);
+        return it != rb + r && *it == q ? k + (int32_t)(it - rb) : -1;
+    };
+    const int32_t li = local(pi), lj = local(pj);
+    if (li < 0 || lj < 0) return false;
+    const int32_t m3 = 3 * (k + r);
+    p->off = S.front_off[(size_t)s] + (int64_t)(3 * lj) * m3 + 3 * li;
+    p->ld = m3;
+    p->pad = 0;
+    return true;
+}
+}  // namespace
+
+extern "C" int dpg_chol_selinv(void* h, void* stream) {
+    return selinv_run(reinterpret_cast<CholDev*>(h), reinterpret_cast<hipStream_t>(stream), nullptr, 0);
+}
+
+extern "C" int dpg_chol_selinv_timed(void* h, void* stream, float* level_ms, int cap) {
+    return selinv_run(reinterpret_cast<CholDev*>(h), reinterpret_cast<hipStream_t>(stream), level_ms, cap);
+}
+
+// host only: the nodes are in range and every pair's block lies in L's pattern (nodes == NULL:
+// all of them in order, n = the graph's size)
+extern "C" int dpg_chol_selinv_check(void* h, const int32_t* nodes, int64_t n, const int32_t* pairs, int64_t n_pairs) {
+    const CholDev* c = reinterpret_cast<const CholDev*>(h);
+    if (!c) return DPG_ERR_STATE;
+    const dpg_chol_sym& S = c->sym;
+    if (n < 0 || n_pairs < 0 || (!nodes && n != 0 && n != S.n) || (n_pairs > 0 && !pairs)) return DPG_ERR_ARG;
+    for (int64_t q = 0; nodes && q < n; ++q)
+        if (nodes[q] < 0 || nodes[q] >= S.n) return DPG_ERR_ARG;
+    SelPick p;
+    for (int64_t q = 0; q < n_pairs; ++q) {
+        const int32_t i = pairs[2 * q], j = pairs[2 * q + 1];
+        if (i < 0 || i >= S.n || j < 0 || j >= S.n || !sel_locate(S, i, j, &p)) return DPG_ERR_ARG;
+    }
+    return DPG_OK;
+}
+
+extern "C" int dpg_chol_selinv_gather(void* h, const int32_t* nodes, int64_t n, const int32_t* pairs, int64_t n_pairs,
+                                      double* out_dev, void* stream) {
+    CholDev* c = reinterpret_cast<CholDev*>(h);
+    const int rc = dpg_chol_selinv_check(h, nodes, n, pairs, n_pairs);
+    if (rc) return rc;
+    if (!c->sel || c->sel_gen != c->build_gen) return DPG_ERR_STATE;
+    const int64_t nb = n + n_pairs;
+    if (nb == 0) return DPG_OK;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const dpg_chol_sym& S = c->sym;
+    std::vector<SelPick>& P = c->h_picks;
+    P.resize((size_t)nb);
+    for (int64_t q = 0; q < n; ++q) {
+        const int32_t v = nodes ? nodes[q] : (int32_t)q;
+        sel_locate(S, v, v, &P[(size_t)q]);
+    }
+    for (int64_t q = 0; q < n_pairs; ++q) sel_locate(S, pairs[2 * q], pairs[2 * q + 1], &P[(size_t)(n + q)]);
+    // (the list is rewritten per request: the previous request's kernel must be done with it)
+    if (hipStreamSynchronize(st) != hipSuccess || dreserve(&c->sel_picks, &c->c_sel_picks, (size_t)nb) ||
+        hipMemcpy(c->sel_picks, P.data(), sizeof(SelPick) * (size_t)nb, hipMemcpyHostToDevice) != hipSuccess)
+        return DPG_ERR_HIP;
+    hipLaunchKernelGGL(chol_selinv_pick, dim3((unsigned)((9 * nb + 255) / 256)), dim3(256), 0, st, c->sel_picks, nb, c->sel,
+                       out_dev);
+    return hipGetLastError() == hipSuccess ? DPG_OK : DPG_ERR_HIP;
+}
+
+// Sigma from the factor in place, then the requested blocks to the host (nodes first, then pairs;
+// [n + n_pairs][9] row-major).  Nothing is written to host_out unless everything succeeded.
+extern "C" int dpg_chol_marginals(void* h, const int32_t* nodes, int64_t n, const int32_t* pairs, int64_t n_pairs,
+                                  double* host_out, void* stream) {
+    CholDev* c = reinterpret_cast<CholDev*>(h);
+    int rc = dpg_chol_selinv_check(h, nodes, n, pairs, n_pairs);
+    if (rc) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int64_t nb = n + n_pairs;
+    if ((rc = dpg_chol_selinv(h, stream))) return rc;
+    if (dreserve(&c->sel_out, &c->c_sel_out, (size_t)(9 * nb))) return DPG_ERR_HIP;
+    if ((rc = dpg_chol_selinv_gather(h, nodes, n, pairs, n_pairs, c->sel_out, stream))) return rc;
+    std::vector<double> tmp((size_t)(9 * nb));
+    int32_t status = 0;
+    if (hipMemcpyAsync(&status, c->status, sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        (nb > 0 && hipMemcpyAsync(tmp.data(), c->sel_out, sizeof(double) * 9 * (size_t)nb, hipMemcpyDeviceToHost, st) !=
+                       hipSuccess) ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return DPG_ERR_HIP;
+    if (status != 0) return DPG_ERR_NUMERIC;
+    for (double v : tmp)
+        if (!(v == v)) return DPG_ERR_NUMERIC;
+    if (nb > 0) memcpy(host_out, tmp.data(), sizeof(double) * 9 * (size_t)nb);
+    return DPG_OK;
+}
+
+extern "C" int64_t dpg_chol_selinv_bytes(void* h) {
+    const CholDev* c = reinterpret_cast<const CholDev*>(h);
+    return c ? (int64_t)(sizeof(double) * (c->c_sel + c->c_sel_work)) : 0;
 }
 
 #ifdef DPG_CHOL_TIMING

@@ -1044,4 +1044,24 @@ int dpg_inc_get_poses(dpg_inc* q, double* poses, int64_t n) {
     return DPG_OK;
 }
 
+// ISAM2::marginalCovariance: the selected inverse of the factor the last update left (read only:
+// L, the tracked factorization and the pending forward-solve state are not touched, so the next
+// update's partial re-elimination continues from the same values)
+int dpg_inc_marginals(dpg_inc* q, const int32_t* nodes, int64_t n, double* cov_out) {
+    if (!q || !q->g.chol || q->V == 0 || q->updates == 0)
+        return set_err(DPG_ERR_STATE, "dpg_inc_marginals: the graph holds no factorization yet");
+    if (dpg_ctx_is_multi(q->ctx)) return set_err(DPG_ERR_STATE, "dpg_inc_marginals: marginals are single-device");
+    if (q->prepared)
+        return set_err(DPG_ERR_STATE, "dpg_inc_marginals: an update is prepared (its analysis has replaced the factor's)");
+    if (!cov_out || n < 0 || (!nodes && n != q->V)) return set_err(DPG_ERR_ARG, "dpg_inc_marginals: bad arguments");
+    if (dpg_chol_selinv_check(q->g.chol, nodes, n, nullptr, 0))
+        return set_err(DPG_ERR_ARG, "dpg_inc_marginals: a node is out of range");
+    if (hipSetDevice(dpg_ctx_device_of(q->ctx)) != hipSuccess) return set_err(DPG_ERR_HIP, "hipSetDevice failed");
+    const int rc = dpg_chol_marginals(q->g.chol, nodes, n, nullptr, 0, cov_out, dpg_ctx_stream_of(q->ctx));
+    if (rc == DPG_ERR_STATE) return set_err(rc, "dpg_inc_marginals: the graph holds no factorization (failed or restored update)");
+    if (rc == DPG_ERR_NUMERIC) return set_err(rc, "dpg_inc_marginals: H is not positive definite");
+    if (rc) return set_err(rc, "dpg_inc_marginals: selected inversion failed");
+    return DPG_OK;
+}
+
 }  // extern "C"

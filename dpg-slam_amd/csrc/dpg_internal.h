@@ -188,6 +188,27 @@ const int32_t* dpg_chol_pos_dev(void* chol);
 const double* dpg_chol_x_dev(void* chol);
 const int32_t* dpg_chol_status_dev(void* chol);
 void dpg_chol_stats(void* chol, double out[6]);
+/* Selected inverse (marginal covariances): the blocks of Sigma = H^-1 inside L's pattern from the
+   factor chol holds now -- whichever of the fused path, the level path or a partial
+   refactorization produced it -- by one root-to-leaves pass, one launch per elimination-tree
+   level, into a Sigma buffer of the fronts' layout (allocated on the first request; the fronts,
+   the pending updates and the tracked factorization are only read).  DPG_ERR_STATE without a
+   factor. */
+int dpg_chol_selinv(void* chol, void* stream);
+/* the same with each level's launch timed by HIP events (roots' level first; blocks until done) */
+int dpg_chol_selinv_timed(void* chol, void* stream, float* level_ms, int cap);
+/* host only: nodes in range, every pair (row node, column node) inside L's pattern (DPG_ERR_ARG
+   otherwise); nodes == NULL with n = the graph's size: every node in order */
+int dpg_chol_selinv_check(void* chol, const int32_t* nodes, int64_t n, const int32_t* pairs, int64_t n_pairs);
+/* the 3x3 blocks (i, i) of the nodes, then (i, j) of the pairs, row-major, out of the Sigma buffer
+   into out_dev[n + n_pairs][9]; the check above runs first, before any launch */
+int dpg_chol_selinv_gather(void* chol, const int32_t* nodes, int64_t n, const int32_t* pairs, int64_t n_pairs,
+                           double* out_dev, void* stream);
+/* dpg_chol_selinv + gather + copy to the host; DPG_ERR_NUMERIC when the factorization failed;
+   host_out is written only on success */
+int dpg_chol_marginals(void* chol, const int32_t* nodes, int64_t n, const int32_t* pairs, int64_t n_pairs,
+                       double* host_out, void* stream);
+int64_t dpg_chol_selinv_bytes(void* chol);   /* Sigma + work buffers, bytes */
 
 /* host work first (pattern, lists, the Cholesky's analysis and plan), then -- after
    hipStreamSynchronize(sync_stream) when given -- the device allocations and uploads */

@@ -40,6 +40,25 @@ def _f64(a) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(a, dtype=np.float64))
 
 
+def _node_list(nodes, what="nodes"):
+    """A node list as int32 [n] (None stays None: every node), rejected before any library call
+    when it is not one-dimensional or not integral."""
+    if nodes is None:
+        return None
+    a = np.asarray(nodes)
+    if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+        raise ValueError(f"{what}: expected a 1-D sequence of node indices, got shape {a.shape} dtype {a.dtype}")
+    return np.ascontiguousarray(a, np.int32)
+
+
+def _pair_list(pairs):
+    """Node pairs as int32 [n, 2], rejected before any library call when shaped otherwise."""
+    a = np.asarray(pairs)
+    if a.ndim != 2 or a.shape[1] != 2 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+        raise ValueError(f"pairs: expected integer node pairs of shape [n, 2], got shape {a.shape} dtype {a.dtype}")
+    return np.ascontiguousarray(a, np.int32)
+
+
 # ------------------------------------------------------------------------- host helpers (R1-R3)
 def scan_to_cloud(ranges, angle_min, angle_max, range_max, laser=(0.2, 0.0, 0.0)) -> np.ndarray:
     r = _f32(ranges)
@@ -387,7 +406,50 @@ class Context:
         st = _abi.GnStats()
         check(lib().dpg_optimize_graph(self.handle, ptr(X, C.c_double), len(X), vptr(F), len(F), C.byref(gp),
                                        C.byref(st)), "dpg_optimize_graph")
+        self._gn_V = len(X)
         return X, st
+
+    # ---- marginal covariances (gtsam::Marginals) ----
+    def marginals(self, poses: np.ndarray, factors: np.ndarray, nodes=None) -> np.ndarray:
+        """dpg_marginal_covariances: the graph linearized at `poses`; the 3x3 covariance of each of
+        `nodes` (None: all), [n, 3, 3], in the pose's own tangent frame."""
+        X = _f64(poses).reshape(-1, 3)
+        F = np.ascontiguousarray(factors, FACTOR_DTYPE)
+        nd = _node_list(nodes)
+        n = len(X) if nd is None else len(nd)
+        out = np.empty((n, 3, 3), np.float64)
+        check(lib().dpg_marginal_covariances(self.handle, ptr(X, C.c_double), len(X), vptr(F), len(F),
+                                             ptr(nd, C.c_int32) if nd is not None else None, n,
+                                             ptr(out, C.c_double)), "dpg_marginal_covariances")
+        self._gn_V = len(X)
+        return out
+
+    def gn_marginals(self, nodes=None) -> np.ndarray:
+        """dpg_gn_marginals: the graph of gn_setup at its current poses (gn_set_poses or the result
+        of gn_run); [n, 3, 3]."""
+        nd = _node_list(nodes)
+        n = int(getattr(self, "_gn_V", 0) or 0) if nd is None else len(nd)
+        out = np.empty((n, 3, 3), np.float64)
+        check(lib().dpg_gn_marginals(self.handle, ptr(nd, C.c_int32) if nd is not None else None, n,
+                                     ptr(out, C.c_double)), "dpg_gn_marginals")
+        return out
+
+    def gn_marginal_pairs(self, pairs) -> np.ndarray:
+        """dpg_gn_marginal_pairs: the joint blocks Sigma(i, j) of node pairs that share a factor; [n, 3, 3]."""
+        pr = _pair_list(pairs)
+        out = np.empty((len(pr), 3, 3), np.float64)
+        check(lib().dpg_gn_marginal_pairs(self.handle, ptr(pr, C.c_int32), len(pr), ptr(out, C.c_double)),
+              "dpg_gn_marginal_pairs")
+        return out
+
+    def gn_marginals_profile(self) -> dict:
+        """dpg_gn_marginals_profile: one all-node marginals call with its parts timed by HIP events."""
+        out = np.zeros(4 + 4096, np.float64)
+        k = int(lib().dpg_gn_marginals_profile(self.handle, ptr(out, C.c_double), len(out)))
+        if k < 0:
+            check(k, "dpg_gn_marginals_profile")
+        return {"assemble_ms": float(out[0]), "factor_ms": float(out[1]), "levels": int(out[2]),
+                "sigma_bytes": int(out[3]), "level_ms": [float(x) for x in out[4:k]]}
 
     # ---- sharded GN step API ----
     def gn_setup(self, V: int, factors: np.ndarray, shard=(0, None), params=None):
@@ -395,6 +457,7 @@ class Context:
         b, e = shard[0], (len(F) if shard[1] is None else shard[1])
         gp = params or _abi.default_gn_params()
         check(lib().dpg_gn_setup(self.handle, V, vptr(F), len(F), b, e, C.byref(gp)), "dpg_gn_setup")
+        self._gn_V = int(V)
         return int(lib().dpg_gn_hb_size(self.handle))
 
     def gn_take_icp(self, first: int, count: int, n_always: int, params=None):
@@ -671,6 +734,16 @@ class IncGraph:
         X = np.zeros((max(n, 1), 3), np.float64)
         check(lib().dpg_inc_get_poses(self.handle, ptr(X, C.c_double), n), "dpg_inc_get_poses")
         return X[:n]
+
+    def marginals(self, nodes=None) -> np.ndarray:
+        """dpg_inc_marginals (ISAM2::marginalCovariance): [n, 3, 3] from the factor as it stands --
+        at the linearization points theta in isam2 mode -- without changing the graph."""
+        nd = _node_list(nodes)
+        n = self.V if nd is None else len(nd)
+        out = np.empty((n, 3, 3), np.float64)
+        check(lib().dpg_inc_marginals(self.handle, ptr(nd, C.c_int32) if nd is not None else None, n,
+                                      ptr(out, C.c_double)), "dpg_inc_marginals")
+        return out
 
     def save(self, path: str):
         """dpg_inc_save: the graph and its context's scan store to one checkpoint file."""

@@ -78,6 +78,10 @@ class GpuBackend:
         self.last_rebuild = self.inc.update(np.asarray(est, np.float64), F)
         return self.inc.poses()
 
+    def marginals(self, nodes=None):
+        """ISAM2::marginalCovariance of the graph as it stands (dpg_inc_marginals): [n, 3, 3]."""
+        return self.inc.marginals(nodes)
+
     def store(self, ranges, geom, offsets, params):
         return api.DpgStore(self.ctx, ranges, geom, offsets=offsets, params=params)
 
@@ -172,6 +176,23 @@ class DpgSLAM:
         disp = api.transform_point(np.array([un[0], un[1], 0], f32), np.array([0, 0, -self.odom_at_last_align[2]], f32))
         rot = api.transform_point(np.array([disp[0], disp[1], 0], f32), np.array([0, 0, ang], f32))
         return np.array([loc[0] + rot[0], loc[1] + rot[1]], f32), f32(ang + dth)
+
+    def GetPoseCovariance(self, node=None):
+        """The 3x3 marginal covariance of a node's pose (default: the latest node), in the pose's own
+        tangent frame (dx, dy, dtheta along its body axes) -- isam_->marginalCovariance(key), which
+        the reference's DpgSLAM does not expose (its start-up check prints gtsam::Marginals,
+        dpg_slam_main.cc:272-279).  Covers the node's graph estimate, not the odometry GetPose adds."""
+        V = len(self.poses)
+        if V == 0:
+            raise ValueError("GetPoseCovariance: the graph has no node yet")
+        k = V - 1 if node is None else int(node)
+        if not 0 <= k < V:
+            raise IndexError(f"GetPoseCovariance: node {node} out of range (the graph has {V} nodes)")
+        fn = getattr(self.be, "marginals", None)
+        if fn is None:
+            raise NotImplementedError(f"GetPoseCovariance needs a `marginals(nodes)` method on the backend; "
+                                      f"{type(self.be).__name__} has none")
+        return np.asarray(fn([k]), np.float64).reshape(3, 3)
 
     def GetMap(self):
         """dpg_slam.cc:555-575."""

@@ -397,6 +397,38 @@ int32_t dpg_gn_factorizations(dpg_ctx* ctx);
 float dpg_gn_last_assemble_ms(dpg_ctx* ctx);
 float dpg_gn_last_solve_ms(dpg_ctx* ctx);
 
+/* ---- marginal covariances (gtsam::Marginals, dpg_slam_main.cc:272-279) ----
+ * The 3x3 diagonal blocks of Sigma = H^-1, H = sum A^T Omega A, and the off-diagonal blocks inside
+ * the Cholesky factor's pattern, by one selected-inversion pass over the factor's fronts on the
+ * device (a small multiple of one factorization) instead of three solves per node.
+ * Tangent space: each block is in the pose's own frame (GTSAM's right perturbation):
+ * rows and columns are (dx, dy, dtheta) along the pose's body axes.  With R the rotation by the
+ * pose's theta, the map-frame xy covariance is R Sxy R^T.
+ * Linearization point: the graph of the last dpg_gn_setup at its CURRENT poses -- those of
+ * dpg_gn_set_poses or the result of dpg_gn_run.  The call re-linearizes there and factors (the loop
+ * may hold an earlier iterate's factor after a chord step); it does not change the poses, the step
+ * history or the factorization count, so dpg_gn_set_poses + dpg_gn_run give bitwise the same
+ * result with or without a marginals call in between.
+ * Errors (cov_out is not written on any of them): DPG_ERR_ARG -- a node out of range, a pair of
+ * nodes that share no factor (only H's own blocks are offered, not what fill adds to L's pattern);
+ * DPG_ERR_STATE -- no graph set up, a graph without a Cholesky (linear_solver = DPG_SOLVER_PCG), or
+ * a context of more than one rank: the multi-device forms (dpg_ctx_create_multi / _virtual / _rank)
+ * do not compute marginals; DPG_ERR_NUMERIC -- H is not positive definite. */
+/* marginalCovariance(key): cov_out[n][9] row-major.  nodes == NULL: every node in order (n = V). */
+int dpg_gn_marginals(dpg_ctx* ctx, const int32_t* nodes, int64_t n, double* cov_out /*[n][9]*/);
+/* joint blocks Sigma(i, j) (rows i, columns j) for pairs that share a factor; Sigma(j, i) is its
+ * transpose */
+int dpg_gn_marginal_pairs(dpg_ctx* ctx, const int32_t* pairs /*[n][2]*/, int64_t n, double* cov_out /*[n][9]*/);
+/* one call: set up the graph (default parameters; it becomes the context's graph), linearize at
+ * poses, factor, invert */
+int dpg_marginal_covariances(dpg_ctx* ctx, const double* poses, int64_t n_nodes, const dpg_factor* factors,
+                             int64_t n_factors, const int32_t* nodes, int64_t n, double* cov_out);
+/* Diagnostic (tools/marginals_probe.py): dpg_gn_marginals of every node, timed by HIP events.
+ * out = {assembly ms, factorization + solve ms, elimination-tree levels, bytes of the Sigma and
+ * work buffers, then the ms of each selected-inversion launch, the roots' level first}; returns
+ * the number of values written (negative: an error). */
+int64_t dpg_gn_marginals_profile(dpg_ctx* ctx, double* out, int64_t cap);
+
 /* ---- re-linearisation sweep (DpgSLAM::reoptimize, dpg_slam.cc:35-120) ---- */
 typedef struct dpg_reopt_params {
     float max_node_dist_within_pass;    /* 5.0 (parameters.h:212) */
@@ -519,6 +551,18 @@ int dpg_inc_update(dpg_inc* g, int64_t n_new, const double* init, const dpg_fact
 int64_t dpg_inc_num_nodes(const dpg_inc* g);
 /* calculateEstimate() of the first n nodes: poses[n][3] */
 int dpg_inc_get_poses(dpg_inc* g, double* poses, int64_t n);
+/* ISAM2::marginalCovariance: cov_out[n][9] from the incremental graph's factor as it stands (the
+ * conventions and errors of dpg_gn_marginals; nodes == NULL: every node, n = dpg_inc_num_nodes).
+ * Nothing is re-linearized or refactored, and L, the state kept for the next partial
+ * re-elimination and the estimates are untouched: updates interleaved with marginals calls give
+ * bitwise the estimates of updates without them.
+ * DPG_INC_ISAM2: the covariance at the linearization points theta that dpg_inc_export returns
+ * (ISAM2's own behaviour: not at the estimate).  DPG_INC_BATCH: at the point of the last update's
+ * last factorization (its last Gauss-Newton iterations may be chord steps).  With
+ * duplicate_factors = 1 the multiplicities are part of H.
+ * DPG_ERR_STATE also: before the first update, after a failed update or dpg_inc_load until the
+ * next successful update. */
+int dpg_inc_marginals(dpg_inc* g, const int32_t* nodes, int64_t n, double* cov_out /*[n][9]*/);
 
 /* Graph checkpoint ("optional binary dump of the graph (poses, edges,
  * measurements)"; the reference keeps dpg_nodes_ with their scans, graph_ and isam_ only in memory,
