@@ -312,7 +312,9 @@ int launch_batch(dpg_ctx* c, const float* ds_dev, const float* full_dev, const i
         kp.lds_tgt = round_up(std::max<int32_t>(maxp, 1), 64);
         rc = dpg_launch_icp_kd(ds_dev, tree_pts, tree_idx, edges_dev, ne, &kp, maxp, res_dev, trace_dev, c->stream);
     } else {
-        kp.lds_tgt = round_up(std::max<int32_t>(max_tgt, 1), 64);
+        // by the larger of the two: the launcher refuses a batch whose largest cloud exceeds the
+        // capacity, and a batch may hold larger sources than targets
+        kp.lds_tgt = round_up(std::max<int32_t>(maxp, 1), 64);
         rc = dpg_launch_icp(ds_dev, edges_dev, ne, &kp, maxp, res_dev, trace_dev, c->stream);
     }
     if (rc) return fail(rc, "ICP kernel launch failed (%d): %s", rc, hipGetErrorString(hipGetLastError()));

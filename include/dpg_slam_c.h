@@ -332,7 +332,10 @@ float dpg_kdtree_build_ms(dpg_ctx* ctx);
 int dpg_ctx_set_icp_variant(dpg_ctx* ctx, int32_t variant);
 /* Angular variant tuning (results are identical for every value): a point whose search window
  * holds more than `cap` candidates is handed to the workgroup's cooperative queue, where a whole
- * wave scans it; 0 scans every window in its own lane.  Default 256. */
+ * wave scans it; 0 scans every window in its own lane.  Default 256.  Tested values: 0, 1 (nearly
+ * every window queued, so the 64-item queue overflows in every iteration and the rest is scanned
+ * in-lane), 8 and 256, each byte-equal to the oracle on near-origin, collinear, tied and
+ * unequal-size clouds and one cloud size per kernel form (tests/test_icp_adversarial.py). */
 int dpg_ctx_set_icp_defer_cap(dpg_ctx* ctx, int32_t cap);
 /* The batched covariance that runs beside the pose graph (dpg_icp_batch_run with covariance, its own
  * stream): at most n workgroups, each taking edges in turn, so the pose graph's kernels find free
