@@ -36,6 +36,7 @@
 #include "dpg_atan2f.h"
 #include "dpg_internal.h"
 #include "dpg_icp_tree.h"
+#include "dpg_icp_fit.h"
 
 namespace {
 
@@ -56,18 +57,33 @@ struct Lds {
     float* fctl;       // [16]
 };
 
-__device__ __forceinline__ size_t align16(size_t x) { return (x + 15) & ~size_t(15); }
+// byte offsets of the seven arrays of Lds, in its order; returns the workgroup's LDS size
+__host__ __device__ inline size_t lds_layout(int lds_tgt, int cells_max, size_t* off /* [7] or null */) {
+    using dpg_icp::align16;
+    size_t o = 0, p[7];
+    p[0] = o; o = align16(o + sizeof(float2) * lds_tgt);
+    p[1] = o; o = align16(o + sizeof(uint64_t) * lds_tgt);
+    p[2] = o; o = align16(o + sizeof(uint64_t) * lds_tgt);
+    p[3] = o; o = align16(o + sizeof(uint32_t) * (cells_max + 1));
+    p[4] = o; o = align16(o + sizeof(uint16_t) * lds_tgt);
+    p[5] = o; o = align16(o + sizeof(double) * 2 * kWaves * (kSums + 2));
+    p[6] = o; o = align16(o + sizeof(float) * 16);
+    if (off)
+        for (int q = 0; q < 7; ++q) off[q] = p[q];
+    return o;
+}
 
 __device__ Lds carve(unsigned char* base, int lds_tgt, int cells_max) {
+    size_t p[7];
+    lds_layout(lds_tgt, cells_max, p);
     Lds L;
-    size_t o = 0;
-    L.tp = reinterpret_cast<float2*>(base + o);       o = align16(o + sizeof(float2) * lds_tgt);
-    L.key0 = reinterpret_cast<uint64_t*>(base + o);   o = align16(o + sizeof(uint64_t) * lds_tgt);
-    L.key1 = reinterpret_cast<uint64_t*>(base + o);   o = align16(o + sizeof(uint64_t) * lds_tgt);
-    L.cells = reinterpret_cast<uint32_t*>(base + o);  o = align16(o + sizeof(uint32_t) * (cells_max + 1));
-    L.tidx = reinterpret_cast<uint16_t*>(base + o);   o = align16(o + sizeof(uint16_t) * lds_tgt);
-    L.wpart = reinterpret_cast<double*>(base + o);    o = align16(o + sizeof(double) * 2 * kWaves * (kSums + 2));
-    L.fctl = reinterpret_cast<float*>(base + o);
+    L.tp = reinterpret_cast<float2*>(base + p[0]);
+    L.key0 = reinterpret_cast<uint64_t*>(base + p[1]);
+    L.key1 = reinterpret_cast<uint64_t*>(base + p[2]);
+    L.cells = reinterpret_cast<uint32_t*>(base + p[3]);
+    L.tidx = reinterpret_cast<uint16_t*>(base + p[4]);
+    L.wpart = reinterpret_cast<double*>(base + p[5]);
+    L.fctl = reinterpret_cast<float*>(base + p[6]);
     return L;
 }
 
@@ -259,20 +275,9 @@ __global__ __launch_bounds__(kThreads) void icp_edges_kernel(const float2* __res
                 trace[((size_t)e * kp.trace_iters + k) * kp.trace_stride + i] = ok ? bi[m] : -1;
             if (ok) dpg_tree::add_pair(acc[m & 1], sx[m], sy[m], bx[m], by[m], bd[m]);
         }
-        dpg_tree::wave_fold(acc[0]);
-        dpg_tree::wave_fold(acc[1]);
-        if (lane == 0) {
-#pragma unroll
-            for (int q = 0; q < kSums; ++q) {
-                L.wpart[wave * (kSums + 2) + q] = acc[0][q];
-                L.wpart[(wave + kWaves) * (kSums + 2) + q] = acc[1][q];
-            }
-        }
-        __syncthreads();
-        // ---- every lane: combine the eight tree waves, fit, converge (uniform control flow) ----
+        // ---- every lane: the eight tree waves' sums, fit, converge (uniform control flow) ----
         double S[kSums];
-#pragma unroll
-        for (int q = 0; q < kSums; ++q) S[q] = dpg_tree::combine(L.wpart, kSums + 2, q);
+        dpg_tree::fold_combine_256(acc, L.wpart, kSums + 2, S);
         // this iteration's key buffer is free again: reset the entries this lane owns
 #pragma unroll
         for (int m = 0; m < PPT; ++m) {
@@ -282,60 +287,19 @@ __global__ __launch_bounds__(kThreads) void icp_edges_kernel(const float2* __res
         const int cnt = (int)S[0];
         last_cnt = cnt;
         if (cnt < kp.min_corr) { converged = 0; status = DPG_ICP_TOO_FEW_CORR; break; }
-        // R5 planar closed form (see oracle rigid_from_sums)
-        const double n = S[0];
-        double a, b;
-        dpg_tree::fit_ab(S, a, b);
-        const double hh = sqrt(a * a + b * b);
-        double c = 1.0, s = 0.0;
-        if (hh > 0.0) { c = a / hh; s = b / hh; }
-        const double mpx = S[2] / n, mpy = S[3] / n, mqx = S[4] / n, mqy = S[5] / n;
-        const double txd = mqx - (c * mpx - s * mpy);
-        const double tyd = mqy - (s * mpx + c * mpy);
-        const float cf = (float)c, sf = (float)s, txf = (float)txd, tyf = (float)tyd;
-        const float nsf = -sf;
+        const dpg_icp::Fit fit = dpg_icp::rigid_from_sums(S);   // R5 (see oracle rigid_from_sums)
+        // R6, decided here and acted on after the move: with the call placed after the move the
+        // compiler lays the loop out differently and the kernel measured 2 % slower
+        const bool stop = dpg_icp::stops(fit, k + 1, prev_mse, kp);
 #pragma unroll
-        for (int m = 0; m < PPT; ++m) {
-            const float x = sx[m], y = sy[m];
-            sx[m] = (cf * x + nsf * y) + txf;
-            sy[m] = (sf * x + cf * y) + tyf;
-        }
-        float Nf[6];
-        Nf[0] = cf * F[0] + nsf * F[3];
-        Nf[1] = cf * F[1] + nsf * F[4];
-        Nf[2] = (cf * F[2] + nsf * F[5]) + txf;
-        Nf[3] = sf * F[0] + cf * F[3];
-        Nf[4] = sf * F[1] + cf * F[4];
-        Nf[5] = (sf * F[2] + cf * F[5]) + tyf;
-#pragma unroll
-        for (int q = 0; q < 6; ++q) F[q] = Nf[q];
+        for (int m = 0; m < PPT; ++m) dpg_icp::move_point(fit, sx[m], sy[m]);
+        dpg_icp::compose(fit, F);
         ++k;
-        const double mse = S[1] / S[0];
-        last_mse = mse;
-        // R6 DefaultConvergenceCriteria
-        if (k >= kp.max_iter) { converged = 1; break; }
-        const float tr = ((cf + cf) + 1.0f) - 1.0f;
-        const double cos_angle = 0.5 * (double)tr;
-        const double tsq = (double)(txf * txf + tyf * tyf);
-        if (cos_angle >= kp.rot_thr && tsq <= kp.eps) { converged = 1; break; }
-        if (fabs(mse - prev_mse) < kp.mse_abs) { converged = 1; break; }
-        prev_mse = mse;
+        last_mse = fit.mse;
+        if (stop) { converged = 1; break; }
+        prev_mse = fit.mse;
     }
-    if (t == 0) {
-        dpg_icp_result R;
-#pragma unroll
-        for (int q = 0; q < 6; ++q) R.T[q] = F[q];
-        R.z[0] = F[2];
-        R.z[1] = F[5];
-        R.z[2] = dpg_atan2f(F[3], F[0]);   // Rotation2Df::fromRotationMatrix -> std::atan2(float, float)
-        R.converged = converged;
-        R.iterations = k;
-        R.n_corr = last_cnt;
-        R.status = status;
-        R.pad = 0;
-        R.fitness = last_mse;
-        results[e] = R;
-    }
+    if (t == 0) dpg_icp::write_result(results + e, F, converged, k, last_cnt, status, last_mse);
 }
 
 // R7: [x, y, yaw] block of d2J_dX2 over index-paired full clouds (s < min(n_data, n_model)).
@@ -451,18 +415,7 @@ __global__ __launch_bounds__(kThreads) void cov6_kernel(const float2* __restrict
 
 }  // namespace
 
-extern "C" size_t dpg_icp_lds_bytes(int32_t lds_tgt, int32_t cells_max) {
-    size_t o = 0;
-    auto a16 = [](size_t x) { return (x + 15) & ~size_t(15); };
-    o = a16(o + sizeof(float2) * lds_tgt);
-    o = a16(o + sizeof(uint64_t) * lds_tgt);
-    o = a16(o + sizeof(uint64_t) * lds_tgt);
-    o = a16(o + sizeof(uint32_t) * (cells_max + 1));
-    o = a16(o + sizeof(uint16_t) * lds_tgt);
-    o = a16(o + sizeof(double) * 2 * kWaves * (kSums + 2));
-    o += sizeof(float) * 16;
-    return a16(o);
-}
+extern "C" size_t dpg_icp_lds_bytes(int32_t lds_tgt, int32_t cells_max) { return lds_layout(lds_tgt, cells_max, nullptr); }
 
 extern "C" int dpg_launch_icp(const float* ds_pts_dev, const dpg_icp_edge* edges_dev, int64_t n_edges,
                               const dpg_icp_kparams* kp, int32_t max_points, dpg_icp_result* results_dev,

@@ -1,4 +1,5 @@
-// dpg_icp_kd.hip -- ICP scan matching, k-d tree variant (the default batched ICP kernel).
+// dpg_icp_kd.hip -- ICP scan matching, k-d tree variant (an A/B reference of the default, the
+// angular kernel in dpg_icp_ang.hip).
 //
 // Same semantics and bit-exact results as the grid kernel in dpg_icp.hip (PCL
 // IterativeClosestPoint + reciprocal KdTreeFLANN correspondences, dpg_slam.cc:387-416), but the
@@ -27,6 +28,7 @@
 #include "dpg_atan2f.h"
 #include "dpg_internal.h"
 #include "dpg_icp_tree.h"
+#include "dpg_icp_fit.h"
 
 namespace {
 
@@ -61,10 +63,7 @@ __device__ __forceinline__ int first_pos(int t, int L, int N) {
     return (int)pos;
 }
 
-__device__ __forceinline__ uint32_t orderable(float f) {
-    const uint32_t b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
+using dpg_icp::orderable;
 
 // one workgroup per node: left-balanced k-d tree of its downsampled cloud
 __global__ __launch_bounds__(kT) void kdtree_build_kernel(const float2* __restrict__ ds_pts,
@@ -138,16 +137,16 @@ struct Lds {
     double* wpart;    // [2 * kW][kSums + 2] (tree waves)
 };
 
-__device__ __forceinline__ size_t a16(size_t x) { return (x + 15) & ~size_t(15); }
-
+// (carve and dpg_icp_kd_lds_bytes below repeat one layout by hand: a shared layout function, as the
+// grid kernel has, made this kernel 2 % slower)
 __device__ Lds carve(unsigned char* base, int cap) {
     Lds L;
     size_t o = 0;
-    L.tp = reinterpret_cast<float2*>(base + o);   o = a16(o + 8 * (size_t)cap);
-    L.sp = reinterpret_cast<float2*>(base + o);   o = a16(o + 8 * (size_t)cap);
-    L.sc = reinterpret_cast<float2*>(base + o);   o = a16(o + 8 * (size_t)cap);
-    L.ti = reinterpret_cast<uint16_t*>(base + o); o = a16(o + 2 * (size_t)cap);
-    L.si = reinterpret_cast<uint16_t*>(base + o); o = a16(o + 2 * (size_t)cap);
+    L.tp = reinterpret_cast<float2*>(base + o);   o = dpg_icp::align16(o + 8 * (size_t)cap);
+    L.sp = reinterpret_cast<float2*>(base + o);   o = dpg_icp::align16(o + 8 * (size_t)cap);
+    L.sc = reinterpret_cast<float2*>(base + o);   o = dpg_icp::align16(o + 8 * (size_t)cap);
+    L.ti = reinterpret_cast<uint16_t*>(base + o); o = dpg_icp::align16(o + 2 * (size_t)cap);
+    L.si = reinterpret_cast<uint16_t*>(base + o); o = dpg_icp::align16(o + 2 * (size_t)cap);
     L.wpart = reinterpret_cast<double*>(base + o);
     return L;
 }
@@ -287,6 +286,7 @@ __global__ __launch_bounds__(kT) void icp_kd_kernel(const float2* __restrict__ d
                 dpg_tree::add_pair(acc[m & 1], qx, qy, tq.x, tq.y, bd);
             }
         }
+        // (the grid kernel's dpg_tree::fold_combine_256, kept in place: 1 % slower here as the call)
         dpg_tree::wave_fold(acc[0]);
         dpg_tree::wave_fold(acc[1]);
         if (lane == 0) {
@@ -303,75 +303,34 @@ __global__ __launch_bounds__(kT) void icp_kd_kernel(const float2* __restrict__ d
         const int cnt = (int)S[0];
         last_cnt = cnt;
         if (cnt < kp.min_corr) { converged = 0; status = DPG_ICP_TOO_FEW_CORR; break; }
-        const double n = S[0];
-        double a, b;
-        dpg_tree::fit_ab(S, a, b);
-        const double hh = sqrt(a * a + b * b);
-        double c = 1.0, s = 0.0;
-        if (hh > 0.0) { c = a / hh; s = b / hh; }
-        const double mpx = S[2] / n, mpy = S[3] / n, mqx = S[4] / n, mqy = S[5] / n;
-        const double txd = mqx - (c * mpx - s * mpy);
-        const double tyd = mqy - (s * mpx + c * mpy);
-        const float cf = (float)c, sf = (float)s, txf = (float)txd, tyf = (float)tyd;
-        const float nsf = -sf;
+        const dpg_icp::Fit fit = dpg_icp::rigid_from_sums(S);
 #pragma unroll
         for (int m = 0; m < PPT; ++m) {
             const int i = t + kT * m;
-            const float x = sx[m], y = sy[m];
-            sx[m] = (cf * x + nsf * y) + txf;
-            sy[m] = (sf * x + cf * y) + tyf;
+            dpg_icp::move_point(fit, sx[m], sy[m]);
             if (i < N) L.sc[i] = make_float2(sx[m], sy[m]);
         }
-        float Nf[6];
-        Nf[0] = cf * F[0] + nsf * F[3];
-        Nf[1] = cf * F[1] + nsf * F[4];
-        Nf[2] = (cf * F[2] + nsf * F[5]) + txf;
-        Nf[3] = sf * F[0] + cf * F[3];
-        Nf[4] = sf * F[1] + cf * F[4];
-        Nf[5] = (sf * F[2] + cf * F[5]) + tyf;
-#pragma unroll
-        for (int q = 0; q < 6; ++q) F[q] = Nf[q];
+        dpg_icp::compose(fit, F);
         ++k;
-        const double mse = S[1] / S[0];
-        last_mse = mse;
+        last_mse = fit.mse;
         __syncthreads();   // moved source points visible before the next reciprocal tests
-        if (k >= kp.max_iter) { converged = 1; break; }
-        const float tr = ((cf + cf) + 1.0f) - 1.0f;
-        const double cos_angle = 0.5 * (double)tr;
-        const double tsq = (double)(txf * txf + tyf * tyf);
-        if (cos_angle >= kp.rot_thr && tsq <= kp.eps) { converged = 1; break; }
-        if (fabs(mse - prev_mse) < kp.mse_abs) { converged = 1; break; }
-        prev_mse = mse;
+        if (dpg_icp::stops(fit, k, prev_mse, kp)) { converged = 1; break; }
+        prev_mse = fit.mse;
     }
-    if (t == 0) {
-        dpg_icp_result R;
-#pragma unroll
-        for (int q = 0; q < 6; ++q) R.T[q] = F[q];
-        R.z[0] = F[2];
-        R.z[1] = F[5];
-        R.z[2] = dpg_atan2f(F[3], F[0]);   // Rotation2Df::fromRotationMatrix -> std::atan2(float, float)
-        R.converged = converged;
-        R.iterations = k;
-        R.n_corr = last_cnt;
-        R.status = status;
-        R.pad = 0;
-        R.fitness = last_mse;
-        results[e] = R;
-    }
+    if (t == 0) dpg_icp::write_result(results + e, F, converged, k, last_cnt, status, last_mse);
 }
 
 }  // namespace
 
 extern "C" size_t dpg_icp_kd_lds_bytes(int32_t cap) {
-    auto al = [](size_t x) { return (x + 15) & ~size_t(15); };
     size_t o = 0;
-    o = al(o + 8 * (size_t)cap);
-    o = al(o + 8 * (size_t)cap);
-    o = al(o + 8 * (size_t)cap);
-    o = al(o + 2 * (size_t)cap);
-    o = al(o + 2 * (size_t)cap);
+    o = dpg_icp::align16(o + 8 * (size_t)cap);
+    o = dpg_icp::align16(o + 8 * (size_t)cap);
+    o = dpg_icp::align16(o + 8 * (size_t)cap);
+    o = dpg_icp::align16(o + 2 * (size_t)cap);
+    o = dpg_icp::align16(o + 2 * (size_t)cap);
     o += sizeof(double) * 2 * kW * (kSums + 2);
-    return al(o);
+    return dpg_icp::align16(o);
 }
 
 extern "C" int dpg_launch_kdtree_build(const float* ds_pts_dev, const int64_t* ds_off_dev, int64_t n_nodes,

@@ -118,6 +118,25 @@ __device__ __forceinline__ double combine(const double* W, int stride, int q) {
            ((W[4 * stride + q] + W[5 * stride + q]) + (W[6 * stride + q] + W[7 * stride + q]));
 }
 
+// The whole tree for a 256-thread workgroup whose thread t carries tree lanes t (acc[0]) and
+// t + 256 (acc[1]): in-wave folds, the eight wave partials into W ([kWaves][stride]), one
+// workgroup barrier, and every thread combines all eight sums.  Called by all 256 threads.
+__device__ __forceinline__ void fold_combine_256(double (&acc)[2][kSums], double* W, int stride, double (&S)[kSums]) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    wave_fold(acc[0]);
+    wave_fold(acc[1]);
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < kSums; ++q) {
+            W[wave * stride + q] = acc[0][q];
+            W[(wave + kWaves / 2) * stride + q] = acc[1][q];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < kSums; ++q) S[q] = combine(W, stride, q);
+}
+
 // one accepted pair (source p moved, target q, fp32 squared distance d) into a lane's sums
 __device__ __forceinline__ void add_pair(double (&acc)[kSums], float sx, float sy, float tx, float ty, float d) {
     const double px = sx, py = sy, qx = tx, qy = ty;
