@@ -1,6 +1,7 @@
 // dpg_chol.h -- GPU supernodal multifrontal Cholesky for the 3x3-block pose-graph system
-// (private, C++).  Symbolic analysis in dpg_chol_sym.cpp, numeric factorization + solves in
-// dpg_chol.hip.
+// (private, C++).  Symbolic analysis in dpg_chol_sym.cpp; host planner (analysis -> index tables and
+// launch parameters, plain C++) in dpg_chol_plan.cpp; kernels and driver (upload, factorization,
+// solves, selected inverse) in dpg_chol.hip.  dpg_chol_plan.h holds what planner and kernels share.
 #ifndef DPG_CHOL_H
 #define DPG_CHOL_H
 
@@ -64,7 +65,8 @@ int dpg_chol_order_nd_sep(int64_t n, const int32_t* pair_lo, const int32_t* pair
                           std::vector<std::vector<int32_t>>& pat, bool par = false);
 int dpg_chol_sym_from_patterns(int64_t n, const std::vector<int32_t>& perm, const std::vector<std::vector<int32_t>>& pat,
                                const dpg_chol_opts* opts, dpg_chol_sym* S);
-// the fused factorization's critical-path estimate (us) of an analysis (the chol_plan ticket model)
+// the fused factorization's critical-path estimate (us) of an analysis: the per-front model the
+// planner orders its tickets by (front_est_us, dpg_chol_plan.h)
 double dpg_chol_critical_path_us(const dpg_chol_sym& S);
 // the same from patterns in CSR form: column p's rows are prow[cp[p] .. cp[p + 1]) (sorted)
 int dpg_chol_sym_from_csr(int64_t n, const int32_t* perm, const int64_t* cp, const int32_t* prow,
@@ -128,8 +130,9 @@ void dpg_chol_blocks_invalidate(void* h);
 void dpg_chol_build_times(void* h, double out[2]);
 // 1 when h factors with the fused DAG kernel (every front fits its LDS budget), 0 on the level path
 int dpg_chol_fused(void* h);
-// the host half of a build alone (no device calls; tools/incsym_bench.cpp times it on the CPU)
+// the host half of a build alone (dpg_chol_plan.cpp; opts NULL: the defaults; tools/incsym_bench.cpp
+// times it on the CPU)
 int dpg_chol_plan_host(int64_t n, const int32_t* pair_lo, const int32_t* pair_hi, int64_t n_pairs,
-                       const dpg_chol_sym* S, double* ms);
+                       const dpg_chol_sym* S, const dpg_chol_opts* opts, double* ms);
 
 #endif

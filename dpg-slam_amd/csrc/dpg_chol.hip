@@ -1,5 +1,10 @@
 // dpg_chol.hip -- supernodal multifrontal Cholesky of the pose-graph normal equations on gfx950.
 //
+// This file: the kernels (factorization, solves, selected inverse) and the host driver (CholDev,
+// the upload, one launch helper per kernel, the solve / selected-inverse / marginals entry points).
+// The host planner that builds every index table the kernels follow is dpg_chol_plan.cpp (plain
+// C++); the records, constants and cost model both sides share are in dpg_chol_plan.h.
+//
 // The CHOLESKY solve that GTSAM runs inside GaussNewtonOptimizer / ISAM2 as a
 // level-scheduled GPU factorization: the symbolic analysis (dpg_chol_sym.cpp) and the per-level
 // task lists run once per sparsity pattern; each GN iteration then runs, per elimination-tree
@@ -30,16 +35,13 @@
 #include <vector>
 
 #include "dpg_chol.h"
+#include "dpg_chol_plan.h"
 #include "dpg_internal.h"
 #include "dpg_gn_pipe.h"
 
-namespace {
+using namespace dpg_chol;   // the plan's records and the tile / panel constants (dpg_chol_plan.h)
 
-constexpr int kT = 256;     // threads per front workgroup
-constexpr int kNB = 48;     // factorization panel width (scalar columns, 16 3x3 blocks)
-constexpr int kSB = 64;     // triangular-solve diagonal block
-constexpr int kCT = 32;     // assembly column tile
-constexpr int kUT = 32;     // trailing-update tile (rows and columns)
+namespace {
 
 // Phase timestamps (timing builds of tools/chol_bench only): workgroup 0 of launch `pid` writes
 // wall_clock64() (100 MHz) into slot [pid][k].
@@ -76,45 +78,14 @@ __device__ unsigned long long g_bwd[16384 * 8];
 #define PROF_END(pid) do { } while (0)
 #endif
 
-struct SnDev {
-    int32_t c0, k, r, nchild;   // k, r in 3x3 blocks
-    int64_t front_off;          // doubles
-    int64_t rows_off;           // into rows / relmap
-    int64_t child_off;          // into child_list
-    int64_t omap_off;
-    int64_t acc_off;            // doubles (3r pending row updates of the forward solve)
-    int32_t omap_n, parent;     // parent supernode, -1 at a root
-    int32_t G, need;            // fused factorization: team size, sum of the children's team sizes
-    int32_t ftask;              // large fronts: first tile task
-    int32_t inv;                // L11^-1 of the front at linv + inv (k3 x k3, column-major), -1: none
-    int32_t seg_off, seg_n;     // backward solve: the row segments by owning supernode (SolveSeg)
-};
-
-// A front's rows (ascending positions) fall into segments owned by its ancestors, the parent's
-// first: the backward solve takes each segment's x as soon as its owner has published it.
-struct SolveSeg { int32_t sn, t0, t1, pad; };   // rows [t0, t1) (blocks) owned by supernode sn
-
-struct OEnt {                   // one upper 3x3 block of H -> its front position
-    int32_t u;                  // block index in the packed hb buffer
-    int16_t a, b;               // local block row / column in the front
-    int32_t tr, pad;            // 1: the front wants H(lo,hi)^T
-};
-
 // ---- numeric factorization: three task-list kernels per elimination-tree level ----
-// (task lists are built once per sparsity pattern in dpg_chol_create)
+// (task lists are built once per sparsity pattern by the planner, dpg_chol_plan.cpp)
 
 // assembly: one workgroup per (front, kCT-column tile), built in LDS: zeroed, the original H
 // blocks scattered in, then each child's update-matrix entries that land in the tile's columns
 // (contiguous child columns [ja, jb), precomputed) added child by child -- within a child the
 // map is injective, so all its entries are in flight at once; an LDS barrier between children
 // fixes the summation order.  The finished tile is stored once, coalesced.
-struct AsmTask {
-    int32_t s, c0;              // front, first column of the tile
-    int32_t om_b, om_e;         // omap entries whose block column meets the tile
-    int32_t ch_off, ch_cnt;     // into AsmChild: the children with columns in the tile
-};
-struct AsmChild { int32_t c, ja, jb, pad; };
-
 __global__ __launch_bounds__(kT) void chol_assemble(const AsmTask* __restrict__ tasks,
                                                     const AsmChild* __restrict__ tchild,
                                                     const SnDev* __restrict__ sns,
@@ -214,12 +185,12 @@ __device__ __forceinline__ Chol3 chol3(double d00, double d10, double d11, doubl
 // row by three so the current block is always p[0..2], and finished entries go straight to HBM.
 // The trailing matrix is left to chol_update.
 template <int NT>
-__global__ __launch_bounds__(NT) void chol_panel(const int2* __restrict__ tasks, const SnDev* __restrict__ sns,
+__global__ __launch_bounds__(NT) void chol_panel(const Task2* __restrict__ tasks, const SnDev* __restrict__ sns,
                                                  double* __restrict__ fronts, int32_t* __restrict__ status, int pid) {
     __shared__ double s_d[6];          // the current diagonal block (lower: 00 10 11 20 21 22)
     __shared__ double4 s_l[kNB];       // L(c, 3b .. 3b+2) of the panel's own rows (w unused)
     const int i = threadIdx.x;
-    const int2 tk = tasks[blockIdx.x];
+    const Task2 tk = tasks[blockIdx.x];
     const SnDev S = sns[tk.x];
     const int m3 = 3 * (S.k + S.r), k3 = 3 * S.k;
     const int j0 = tk.y, w = min(kNB, k3 - j0), R = m3 - j0;
@@ -292,13 +263,13 @@ __global__ __launch_bounds__(NT) void chol_panel(const int2* __restrict__ tasks,
 
 // update: one workgroup per 32x32 tile (rows i0.., cols l0..) of a front's trailing lower
 // triangle: F(i, l) -= sum_c L(i, j0 + c) L(l, j0 + c) over the panel's w columns.
-__global__ __launch_bounds__(kT) void chol_update(const int4* __restrict__ tasks, const SnDev* __restrict__ sns,
+__global__ __launch_bounds__(kT) void chol_update(const Task4* __restrict__ tasks, const SnDev* __restrict__ sns,
                                                   double* __restrict__ fronts, int pid) {
     PROF_BEGIN(pid);
     PROF_MARK(pid, 0);
     __shared__ double A[kNB][33], B[kNB][33];
     const int tid = threadIdx.x;
-    const int4 tk = tasks[blockIdx.x];
+    const Task4 tk = tasks[blockIdx.x];
     const SnDev S = sns[tk.x];
     const int m3 = 3 * (S.k + S.r), k3 = 3 * S.k;
     const int j0 = tk.y, w = min(kNB, k3 - j0), i0 = tk.z, l0 = tk.w;
@@ -417,20 +388,18 @@ __device__ __forceinline__ double group16_sum(double a) {
 // fronts up to 192 pivot columns); step i broadcasts x_i from its owner (one readlane) and every lane
 // adds L(r, i) x_i to its rows r > i.  L's columns come straight from the fronts (L2), 16 steps'
 // worth loaded ahead into registers; no LDS, so many columns run per compute unit.
-constexpr int kInvCols = 4;              // columns (waves) per workgroup
 constexpr int kInvThreads = 64 * kInvCols;
-constexpr int kInvMaxQ = 3;              // rows per lane
 constexpr int kInvAhead = 16;            // steps of L loaded ahead
 __device__ __forceinline__ double rdlane_(double v, int l) {
     const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
     const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
     return __hiloint2double(hi, lo);
 }
-__global__ __launch_bounds__(kInvThreads) void chol_inv_l11(const int2* __restrict__ tasks, const SnDev* __restrict__ sns,
+__global__ __launch_bounds__(kInvThreads) void chol_inv_l11(const Task2* __restrict__ tasks, const SnDev* __restrict__ sns,
                                                             const double* __restrict__ fronts, double* __restrict__ linv,
                                                             const int32_t* gate) {
     if (gate_off(gate, 1)) return;
-    const int2 tk = tasks[blockIdx.x];
+    const Task2 tk = tasks[blockIdx.x];
     const SnDev S = sns[tk.x];
     const int lane = threadIdx.x & 63;
     const int j = tk.y + (int)(threadIdx.x >> 6);      // this wave's column
@@ -616,7 +585,6 @@ __device__ __forceinline__ double run_chain(const double* D, double rl, double v
 // inv(B) (forward) or inv(B)^T (backward) as a mat-vec: independent products, 4 partial sums.
 // Layout: dinv[(3 c0 + jb + col) * kSB + row] = inv(B)[row][col] for row, col < bw, B = the front's
 // diagonal block at (jb, jb) (bw = min(kSB, k3 - jb)); one kSB-double column per pivot column.
-constexpr int kDL = kSB + 1;   // leading dimension of D in the inverse path (transposed stores conflict-free)
 
 // 8 consecutive doubles of LDS (16-B aligned, OFF bytes past base) into registers: four
 // ds_read_b128 and one wait as inline asm with immediate offsets; `dep` is a fake operand that
@@ -674,10 +642,10 @@ struct InvCol {
 };
 
 // one wave per diagonal block; every block padded to 64 columns (one code path)
-__global__ __launch_bounds__(64) void chol_inv_diag(const int2* __restrict__ blocks, const SnDev* __restrict__ sns,
+__global__ __launch_bounds__(64) void chol_inv_diag(const Task2* __restrict__ blocks, const SnDev* __restrict__ sns,
                                                     const double* __restrict__ fronts, double* __restrict__ dinv) {
     __shared__ __attribute__((aligned(16))) double B[kSB * kSB];
-    const int2 b = blocks[blockIdx.x];   // (front, jb)
+    const Task2 b = blocks[blockIdx.x];   // (front, jb)
     const SnDev S = sns[b.x];
     const int m3 = 3 * (S.k + S.r), k3 = 3 * S.k, jb = b.y, bw = min(kSB, k3 - jb);
     const int lane = threadIdx.x;
@@ -1030,7 +998,6 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(2))) void ch
 // segment by segment as the rows' owners publish (the highest ancestor's rows first, the parent's
 // last: after the parent's signal only its own rows remain), then solves its diagonal blocks and
 // publishes its own x.  Its L is staged in LDS before any wait (Stage).
-constexpr int kMaxSeg = 32;   // row segments held in LDS (a front with more waits for its parent, then takes every row)
 
 // z -= L21[rows r0..r1)^T x_r[r0..r1) (scalar rows of the L21 block)
 template <bool kFull>
@@ -1203,30 +1170,10 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(2))) void ch
 // >= k3) and the pending row updates -- is stored write-through (sc1, agent-scope relaxed stores)
 // and read back with sc1 loads; every storing wave drains, the workgroup synchronises, ONE lane
 // adds to the parent's counter; the consumer polls relaxed, then one agent-scope acquire.
-constexpr int kFT = 512;    // threads per front workgroup
-constexpr int kFNB = 24;    // panel width (scalar columns = 8 3x3 blocks)
-constexpr int kSmall = 96;  // fronts up to this many rows are assembled + factored entirely in LDS
-constexpr int kMaxCh = 8;   // ... if they have at most this many children
+// (kFT threads, kFNB-column panels, the kSmall / kMaxCh rule, teams of up to kGmax and the LDS
+// carve fused_rp / kFScr / fused_lds_doubles: dpg_chol_plan.h)
 constexpr int kPF = (kSmall * (kSmall + 1) / 2 + kFT - 1) / kFT;   // per-thread prefetch slots per child
 constexpr int kPFL = 4;      // large fronts: entries in flight per thread in the extend-add / publish rounds
-constexpr int kGmax = 32;    // largest team (workgroups per front)
-
-struct ChMeta { int64_t front_off, acc_off, rows_off; int32_t k, r; };
-
-
-
-
-// LDS carve of the factorization phase (doubles): panel [kFNB][Rp] with row offset `off` so that
-// trailing rows start 32-B aligned, L_top column-major [kFNB][kFNB], 1/diag, step scratch.
-__host__ __device__ inline int fused_rp(int R, int off) { return (R + off + 3) & ~3; }
-constexpr int kFScr = kFNB * kFNB + 8 * (kFNB / 3) + 384;   // L_top, 3x3 inverses, POTRF exchange
-__host__ __device__ inline size_t fused_lds_doubles(int m3, int k3, bool db) {
-    // right-hand side | scratch | one or two panel buffers (the first also holds the assembly tile)
-    const size_t large = ((m3 + 1) & ~1) + kFScr + (db ? 2 : 1) * (size_t)kFNB * fused_rp(m3, 3);
-    (void)k3;
-    const size_t small = m3 <= kSmall ? (size_t)m3 * m3 + m3 + (kMaxCh * sizeof(ChMeta) + kMaxCh * (kSmall / 3) * 4 + 7) / 8 : 0;
-    return 2 + std::max(small, large);
-}
 
 // packed lower triangle of an n x n matrix, column-major: entry e -> (row i, column j), i >= j
 __device__ __forceinline__ void tri_ij(int e, int n, int& i, int& j) {
@@ -1421,18 +1368,32 @@ struct Tiles {
     __device__ int c1(int t) const { return t < np ? min(kFNB * t + kFNB, k3) : min(k3 + kFNB * (t - np + 1), m3); }
 };
 
-// per (large front, tile): the H blocks and the children's column ranges that land in the tile
-struct FTask { int32_t om_b, om_e, ch_off, ch_cnt; };
-struct FChild { int32_t ja, jb, k, r; int64_t front_off, rows_off; };
+// The frame of pivot panel q of a large front: front columns [j0, j0 + w), rows j0 .. m3 (R of
+// them).  In LDS, element (row i, column c) of the frame sits at P[c * Rp + off + i], `off` chosen
+// so that the rows below the w x w top block start 32-B aligned.  Between workgroups a column goes
+// as npc aligned 16-B pairs of front elements (publish_panel stores what load_panel loads).
+struct PanelFrame {
+    int m3, j0, w, R, off, Rp, npc;
+    __device__ __forceinline__ PanelFrame(const Tiles& T, int q)
+        : m3(T.m3), j0(kFNB * q), w(min(kFNB, T.k3 - j0)), R(T.m3 - j0), off((4 - (w & 3)) & 3), Rp(fused_rp(R, off)),
+          npc((R + 2) >> 1) {}
+    // pair e of the w * npc: its column, its first row in the frame (-1: the element before the
+    // column segment) and its front element (even)
+    struct Pair { int c, i0; uint32_t addr; };
+    __device__ __forceinline__ Pair pair(int e) const {
+        const int c = e / npc, k = e - c * npc;
+        const uint32_t a = (uint32_t)((j0 + c) * m3 + j0);
+        return Pair{c, 2 * k - (int)(a & 1u), (a & ~1u) + 2u * k};
+    }
+};
 
 // Panel q of a large front, in LDS (P, the panel frame: column c of the tile at P[c * Rp + off + i],
 // rows i >= c valid, zeros above): POTRF of the top w x w block, TRSM of the rows below, L_top
 // copied back.  `scr` holds L_top, the 3x3 inverses and the POTRF column exchange.
 __device__ void factor_lds(int q, int s, const Tiles& T, double* P, double* scr, bool& bad) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int k3 = T.k3, m3 = T.m3;
-    const int j0 = kFNB * q, w = min(kFNB, k3 - j0), R = m3 - j0;
-    const int off = (4 - (w & 3)) & 3, Rp = fused_rp(R, off);
+    const PanelFrame f(T, q);
+    const int w = f.w, R = f.R, off = f.off, Rp = f.Rp;
     double* Lt = scr;
     double* rdg = Lt + kFNB * kFNB;
     int* flg = reinterpret_cast<int*>(rdg + 8 * (kFNB / 3));   // [kFNB / 3] step epochs (zeroed by the chain's start)
@@ -1531,17 +1492,15 @@ __device__ void factor_lds(int q, int s, const Tiles& T, double* P, double* scr,
 // the factored panel q (LDS) -> its front columns, write-through, then the panel flag
 __device__ void publish_panel(int q, int s, const Tiles& T, double* F, const double* P, int32_t* pflag) {
     const int tid = threadIdx.x;
-    const int j0 = kFNB * q, w = min(kFNB, T.k3 - j0), R = T.m3 - j0;
-    const int off = (4 - (w & 3)) & 3, Rp = fused_rp(R, off);
+    const PanelFrame f(T, q);
+    const int R = f.R;
     const auto rs = front_rsrc(F, T.m3);
-    const int npc = (R + 2) >> 1;   // aligned pairs per column segment (rows j0 .. m3)
-    for (int e = tid; e < w * npc; e += kFT) {
-        const int c = e / npc, k = e - c * npc;
-        const uint32_t a = (uint32_t)((j0 + c) * T.m3 + j0);
-        const int i0 = 2 * k - (int)(a & 1u);   // the pair's first row (segment frame)
+    for (int e = tid; e < f.w * f.npc; e += kFT) {
+        const PanelFrame::Pair pr = f.pair(e);
+        const int c = pr.c, i0 = pr.i0;
         if (i0 + 1 < c || i0 >= R) continue;   // wholly above the diagonal, or past the column
-        const double* pc = P + c * Rp + off;
-        st2_sc1(rs, (a & ~1u) + 2u * k, i0 >= c ? pc[i0] : 0.0, i0 + 1 < R ? pc[i0 + 1] : 0.0);
+        const double* pc = P + c * f.Rp + f.off;
+        st2_sc1(rs, pr.addr, i0 >= c ? pc[i0] : 0.0, i0 + 1 < R ? pc[i0 + 1] : 0.0);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -1554,29 +1513,26 @@ __device__ void publish_panel(int q, int s, const Tiles& T, double* F, const dou
 template <bool SC1>
 __device__ void load_panel(int p, const Tiles& T, double* F, double* P) {
     const int tid = threadIdx.x;
-    const int j0 = kFNB * p, w = min(kFNB, T.k3 - j0), R = T.m3 - j0;
-    const int off = (4 - (w & 3)) & 3, Rp = fused_rp(R, off);
+    const PanelFrame f(T, p);
+    const int j0 = f.j0, w = f.w, R = f.R, off = f.off, Rp = f.Rp;
     if (SC1) {   // 16-B sc1 loads of the aligned pairs (publish_panel's cover of each column segment)
         const auto rs = front_rsrc(F, T.m3);
-        const int npc = (R + 2) >> 1, tot = w * npc;
+        const int tot = w * f.npc;
         constexpr int kB2 = 8;
         for (int e0 = 0; e0 < tot; e0 += kFT * kB2) {
             double2 v[kB2];
 #pragma unroll
             for (int q = 0; q < kB2; ++q) {
                 const int e = e0 + tid + kFT * q;
-                const int c = e / npc, k = e - c * npc;
-                const uint32_t a = (uint32_t)((j0 + c) * T.m3 + j0);
-                const int i0 = 2 * k - (int)(a & 1u);
+                const PanelFrame::Pair pr = f.pair(e);
                 v[q] = make_double2(0.0, 0.0);
-                if (e < tot && i0 < R && i0 + 1 >= c) v[q] = ld2_sc1(rs, (a & ~1u) + 2u * k);
+                if (e < tot && pr.i0 < R && pr.i0 + 1 >= pr.c) v[q] = ld2_sc1(rs, pr.addr);
             }
 #pragma unroll
             for (int q = 0; q < kB2; ++q) {
                 const int e = e0 + tid + kFT * q;
-                const int c = e / npc, k = e - c * npc;
-                const uint32_t a = (uint32_t)((j0 + c) * T.m3 + j0);
-                const int i0 = 2 * k - (int)(a & 1u);
+                const PanelFrame::Pair pr = f.pair(e);
+                const int c = pr.c, i0 = pr.i0;
                 if (e < tot) {
                     double* pc = P + c * Rp + off;
                     if (i0 >= 0 && i0 < R) pc[i0] = i0 >= c ? v[q].x : 0.0;
@@ -1611,8 +1567,8 @@ __device__ void load_panel(int p, const Tiles& T, double* F, double* P) {
 template <bool WT, bool SC1 = false>
 __device__ void update_tile(int t, int p, const Tiles& T, double* F, const double* P) {
     const int tid = threadIdx.x;
-    const int m3 = T.m3, j0 = kFNB * p, w = min(kFNB, T.k3 - j0), R = m3 - j0;
-    const int off = (4 - (w & 3)) & 3, Rp = fused_rp(R, off);
+    const PanelFrame f(T, p);
+    const int m3 = f.m3, j0 = f.j0, w = f.w, R = f.R, off = f.off, Rp = f.Rp;
     const int l0 = T.c0(t) - j0, l1 = T.c1(t) - j0;   // the tile's columns, panel frame
     const int g0 = ((l0 + off) & ~3) - off;            // 4-aligned group start (<= l0)
     const int ncg = (l1 - g0 + 3) >> 2, nrg = (R - g0 + 3) >> 2;
@@ -1667,6 +1623,7 @@ __device__ void update_tile(int t, int p, const Tiles& T, double* F, const doubl
 __device__ void update_next_lds(int p, const Tiles& T, const double* Pc, double* Pn) {
     const int tid = threadIdx.x;
     const int j0 = kFNB * p, R = T.m3 - j0, Rp = fused_rp(R, 0);   // panel p is full: off 0
+    // panel p + 1's frame relative to panel p's (PanelFrame(T, p + 1), spelled from R)
     const int j1 = j0 + kFNB, w1 = min(kFNB, T.k3 - j1), R1 = R - kFNB;
     const int off1 = (4 - (w1 & 3)) & 3, Rp1 = fused_rp(R1, off1);
     const int ncg = (w1 + 3) >> 2, nrg = (R1 + 3) >> 2;
@@ -1705,8 +1662,8 @@ __device__ void update_next_lds(int p, const Tiles& T, const double* Pc, double*
 // forward solve folded in: y of panel p's rows (one wave), then the rows below (bv, LDS)
 __device__ void rhs_panel(int p, const Tiles& T, const double* P, double* bv) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int j0 = kFNB * p, w = min(kFNB, T.k3 - j0), R = T.m3 - j0;
-    const int off = (4 - (w & 3)) & 3, Rp = fused_rp(R, off);
+    const PanelFrame f(T, p);
+    const int j0 = f.j0, w = f.w, R = f.R, off = f.off, Rp = f.Rp;
     if (wave == 0) {
         double bl = lane < w ? bv[j0 + lane] : 0.0;
         for (int c = 0; c < w; ++c) {
@@ -2172,7 +2129,11 @@ int dreserve(T** d, size_t* cap, size_t n) {
 struct CholDev {
     dpg_chol_opts opts;   // the context's solver options at creation
     dpg_chol_sym sym;
-    int64_t n = 0;
+    // the plan of `sym` (dpg_chol_plan.cpp): host arrays, sizes and launch parameters.  A plan and
+    // its upload may run on different threads, one after the other; dpg_chol_plan_blocks fills its
+    // H-block buckets beside the next analysis's derivation.
+    CholPlan plan;
+    // the plan's arrays on the device (all in `arena`)
     SnDev* sns = nullptr;
     OEnt* omap = nullptr;
     int32_t* child_list = nullptr;
@@ -2180,6 +2141,19 @@ struct CholDev {
     int32_t* rows = nullptr;
     int32_t* perm = nullptr;
     int32_t* pos = nullptr;
+    int32_t* order_fwd = nullptr;      // forward solve: fronts in the tickets' order
+    int32_t* order_fac = nullptr;      // fused factorization tickets (front * 64 + member)
+    int32_t* order_bwd = nullptr;
+    FTask* ftasks = nullptr;           // large fronts: per-tile assembly lists
+    FChild* fchild = nullptr;
+    SolveSeg* segs = nullptr;
+    Task2* dblocks = nullptr;          // (front, jb) of every diagonal block
+    Task2* inv_tasks = nullptr;        // chol_inv_l11: (front, first column) per workgroup
+    AsmTask* asm_tasks = nullptr;      // level path
+    AsmChild* asm_child = nullptr;
+    Task2* panel_tasks = nullptr;
+    Task4* upd_tasks = nullptr;
+    // values
     double* fronts = nullptr;
     double* acc = nullptr;
     double* ysol = nullptr;
@@ -2187,40 +2161,8 @@ struct CholDev {
     int32_t* status = nullptr;
     double* dinv = nullptr;            // inverted diagonal blocks of the solves ([3n][kSB])
     double* linv = nullptr;            // L11^-1 of the large fronts (SnDev.inv offsets)
-    int2* inv_tasks = nullptr;         // chol_inv_l11: (front, first column) per workgroup
-    int64_t n_inv_tasks = 0, linv_total = 0;
-    size_t lds_inv = 0, c_linv = 0;
-    int2* dblocks = nullptr;           // (front, jb) of every diagonal block
-    int64_t n_dblocks = 0;
-    bool use_dinv = false;             // DPG_SOLVE_DINV=1: inverted diagonal blocks (measured slower)
-    std::vector<int32_t> level_ptr;
-    std::vector<size_t> lds_solve;   // per level
-    int64_t nnzb_upper = 0;
-    // factorization task lists (device) and the per-level launch plan (host)
-    int32_t* order_fwd = nullptr;      // fronts bottom-up (level order) / top-down
-    int32_t* order_fac = nullptr;      // fused factorization tickets (front * 64 + member)
-    FTask* ftasks = nullptr;           // large fronts: per-tile assembly lists
-    FChild* fchild = nullptr;
-    int64_t n_tickets = 0;
-    int32_t* order_bwd = nullptr;
-    SolveSeg* segs = nullptr;
-    int32_t* sync = nullptr;           // [ticket_f, cnt_f[ns], ticket_b, done_b[ns]], zeroed per solve
-    size_t sync_bytes = 0;
-    size_t lds_solve_max = 0;
-    int32_t solve_stage = 0;   // R: LDS staging region of the solves, doubles (Stage)
-    int32_t solve_maxseg = 0;  // backward: fronts with more row segments wait for the parent (<= kMaxSeg)
-    AsmTask* asm_tasks = nullptr;
-    AsmChild* asm_child = nullptr;
-    int2* panel_tasks = nullptr;
-    int4* upd_tasks = nullptr;
-    struct Step { int32_t panel_off, panel_cnt, rpt /* panel rows / kT, rounded up */, max_rows, upd_off, upd_cnt; };
-    struct Level { int32_t asm_off, asm_cnt; size_t lds_asm; std::vector<Step> steps; };
-    std::vector<Level> plan;
-    int64_t n_launches = 0;
-    // fused DAG factorization + forward solve (used when every front fits its LDS budget)
-    bool fused = false;
-    size_t lds_fused = 0;
-    bool fused_db = true;
+    size_t c_linv = 0;
+    int32_t* sync = nullptr;           // plan.sync_bytes of counters and flags, zeroed per solve (SyncWords)
     // L11^-1 (chol_inv_l11): valid for the last factorization (inv_valid: computed by an ungated
     // solve); the gated loop computes it on `aux` beside each refactoring iteration's backward solve
     // and its chord iterations wait for it (ev_inv of the previous iteration)
@@ -2244,7 +2186,7 @@ struct CholDev {
     double* fac_ysol = nullptr;
     double* fac_acc = nullptr;
     dpg_chol_sym fac_sym;
-    std::vector<int32_t> cur_G, fac_G;
+    std::vector<int32_t> fac_G;   // (the current analysis's: plan.cur_G)
     std::vector<uint8_t> h_keep;
     std::vector<int32_t> h_old;
     std::vector<int64_t> h_runs;
@@ -2257,8 +2199,6 @@ struct CholDev {
     hipEvent_t pev = nullptr;     // after that copy (the staging buffer's next rewrite waits for it)
     bool pev_set = false;
     int64_t pstats[4] = {0, 0, 0, 0};   // last solve: fronts refactored, kept, doubles moved, host ns of the pick
-    void* host = nullptr;         // CholHost of the build in progress (a plan and its upload may run
-                                  // on different threads, one after the other)
     // selected inverse (dpg_chol_selinv): nothing here is allocated or built before the first
     // request.  `sel` has the fronts' layout; `sel_work` holds [Z; Y] of the fronts too large for
     // LDS (sel_woff); sel_list = level_list on the device.  The lists belong to the analysis
@@ -2276,15 +2216,13 @@ struct CholDev {
     std::vector<hipEvent_t> sel_ev;
 };
 
-void free_host(void* p);
-
 // a new analysis in; *S gets back one whose buffers the caller reuses.  With tracking, the analysis
 // of the last factorization moves to fac_sym instead (the partial refactorization compares with it)
 void take_sym(CholDev* c, dpg_chol_sym* S) {
     c->has_factor = false;   // (the values in fronts belong to the analysis leaving)
     if (c->track && c->sym_is_fac) {
         std::swap(c->fac_sym, c->sym);
-        c->fac_G.swap(c->cur_G);
+        c->fac_G.swap(c->plan.cur_G);
         c->sym_is_fac = false;
     }
     std::swap(c->sym, *S);
@@ -2309,7 +2247,6 @@ extern "C" void dpg_chol_destroy(void* h) {
     for (hipEvent_t e : c->ev_inv)
         if (e) (void)hipEventDestroy(e);
     if (c->aux) (void)hipStreamDestroy(c->aux);
-    free_host(c->host);
     delete c;
 }
 
@@ -2352,551 +2289,12 @@ double wall_ms() {
     return (double)ts.tv_sec * 1e3 + (double)ts.tv_nsec * 1e-6;
 }
 
-// host-side structures of one build (kept between builds: the incremental graph rebuilds per update)
-struct CholHost {
-    struct Blk { int32_t row, u, tr; };   // an upper block of H in its column's bucket
-    struct Blk4 { int32_t row, col, u, tr; };
-    std::vector<int64_t> colptr;
-    std::vector<Blk> ent;
-    std::vector<Blk4> byrow;
-    std::vector<int32_t> lidx, lstamp;
-    std::vector<int64_t> om_ptr, om_cur;
-    std::vector<OEnt> omap;
-    std::vector<SnDev> sns;
-    std::vector<FTask> ftasks;
-    std::vector<FChild> fchild;
-    std::vector<double> prio, hgt;
-    std::vector<int32_t> hcnt;
-    std::vector<SolveSeg> segs;
-    std::vector<std::pair<double, int32_t>> key;
-    std::vector<int32_t> fo, bwd, order_fac, cuts;
-    std::vector<AsmTask> asm_t;
-    std::vector<AsmChild> asm_c;
-    std::vector<int2> panel_t;
-    std::vector<int4> upd_t;
-    std::vector<int2> dblocks;
-    std::vector<int2> inv_t;            // chol_inv_l11 tasks (front, first column)
-    std::vector<int32_t> tcnt, tfill;   // per-tile child counts / fill cursors of one large front
-    std::vector<char> tused;
-    int64_t acc_total = 0;
-    // colptr / ent built ahead by dpg_chol_plan_blocks (the incremental prepare runs it beside the
-    // symbolic derivation) for a graph of blocks_n nodes and blocks_np pairs; the next plan takes them
-    bool blocks_ready = false;
-    int64_t blocks_n = -1, blocks_np = -1;
-};
-
-#ifdef DPG_PLAN_TIMING
-double g_plan_t[8];
-#define PLAN_T(k) g_plan_t[k] += wall_ms()
-#else
-#define PLAN_T(k) do { } while (0)
-#endif
-
-// A child's update rows j = 0 .. 3r-1 land in parent front row 3 rm[j / 3] + j % 3, increasing in
-// j: the first j landing at or after parent row c.
-inline int32_t first_at_or_after(const int32_t* rm, int32_t r, int32_t c) {
-    int32_t lo = 0, hi = 3 * r;
-    while (lo < hi) {
-        const int32_t mid = (lo + hi) / 2;
-        if (3 * rm[mid / 3] + mid % 3 < c) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
-// H's upper blocks bucketed by column position, each bucket in ascending row order (the plan's
-// first part; pos / perm: the ordering -- the symbolic analysis's, or the incremental state's it
-// will copy)
-void plan_blocks(CholHost& H, int64_t n, const int32_t* pos, const int32_t* perm, const int32_t* pair_lo,
-                 const int32_t* pair_hi, int64_t n_pairs) {
-    std::vector<int64_t>& colptr = H.colptr;
-    colptr.assign((size_t)n + 1, 0);
-    for (int64_t p = 0; p < n; ++p) colptr[(size_t)p + 1] = 1;   // the diagonal block
-    for (int64_t q = 0; q < n_pairs; ++q)
-        colptr[(size_t)std::min(pos[(size_t)pair_lo[q]], pos[(size_t)pair_hi[q]]) + 1]++;
-    for (int64_t p = 0; p < n; ++p) colptr[(size_t)p + 1] += colptr[(size_t)p];
-    std::vector<CholHost::Blk>& ent = H.ent;
-    ent.resize((size_t)colptr[(size_t)n]);
-    {
-        // two counting sorts: the blocks by row (the pairs' later position; the diagonal block is
-        // its column's first row), then stably into their column buckets -- each bucket comes out
-        // in ascending row order without a per-bucket sort
-        std::vector<int64_t>& rptr = H.om_cur;
-        rptr.assign((size_t)n + 1, 0);
-        for (int64_t p = 0; p < n; ++p) rptr[(size_t)p + 1] = 1;
-        for (int64_t q = 0; q < n_pairs; ++q)
-            rptr[(size_t)std::max(pos[(size_t)pair_lo[q]], pos[(size_t)pair_hi[q]]) + 1]++;
-        for (int64_t p = 0; p < n; ++p) rptr[(size_t)p + 1] += rptr[(size_t)p];
-        std::vector<CholHost::Blk4>& byrow = H.byrow;
-        byrow.resize(ent.size());
-        for (int64_t p = 0; p < n; ++p) byrow[(size_t)rptr[(size_t)p]++] = CholHost::Blk4{(int32_t)p, (int32_t)p, perm[(size_t)p], 0};
-        for (int64_t q = 0; q < n_pairs; ++q) {
-            const int32_t plo = pos[(size_t)pair_lo[q]], phi = pos[(size_t)pair_hi[q]];
-            // front wants A(later, earlier) = H(later_node, earlier_node); hb holds H(lo, hi)
-            const int32_t r = std::max(plo, phi);
-            byrow[(size_t)rptr[(size_t)r]++] = CholHost::Blk4{r, std::min(plo, phi), (int32_t)(n + q), plo > phi ? 0 : 1};
-        }
-        rptr.assign(colptr.begin(), colptr.end() - 1);   // column cursors
-        for (const CholHost::Blk4& b : byrow) ent[(size_t)rptr[(size_t)b.col]++] = CholHost::Blk{b.row, b.u, b.tr};
-    }
-    H.blocks_n = n;
-    H.blocks_np = n_pairs;
-}
-
-// Host half of chol_build: every device structure, in H; the plan fields of c.
-int chol_plan(CholDev* c, int64_t n, const int32_t* pair_lo, const int32_t* pair_hi, int64_t n_pairs, CholHost& H) {
-    const dpg_chol_sym& S = c->sym;
-    c->lds_fused = 0;
-    c->n_launches = 0;
-    c->n = n;
-    c->nnzb_upper = n + n_pairs;
-    PLAN_T(0);
-    // omap: every upper block of H -> (front, local block row, local block col, transpose), grouped
-    // by front, each front's entries by (column, row): the blocks are bucketed by column position
-    // (counting sort), each bucket sorted by row, and the fronts walked column by column
-    const bool pre = H.blocks_ready && H.blocks_n == n && H.blocks_np == n_pairs;
-    H.blocks_ready = false;
-#ifdef DPG_PLAN_VERIFY
-    if (pre) {   // the prebuilt buckets must equal this plan's own
-        const std::vector<int64_t> cp0 = H.colptr;
-        const std::vector<CholHost::Blk> e0 = H.ent;
-        plan_blocks(H, n, S.pos.data(), S.perm.data(), pair_lo, pair_hi, n_pairs);
-        bool same = cp0 == H.colptr && e0.size() == H.ent.size();
-        for (size_t k = 0; same && k < e0.size(); ++k)
-            same = e0[k].row == H.ent[k].row && e0[k].u == H.ent[k].u && e0[k].tr == H.ent[k].tr;
-        if (!same) { fprintf(stderr, "DPG_PLAN_VERIFY: prebuilt H-block buckets differ\n"); abort(); }
-    }
-#endif
-    if (!pre) plan_blocks(H, n, S.pos.data(), S.perm.data(), pair_lo, pair_hi, n_pairs);
-    const std::vector<int64_t>& colptr = H.colptr;
-    const std::vector<CholHost::Blk>& ent = H.ent;
-    PLAN_T(1);
-    std::vector<int64_t>& om_ptr = H.om_ptr;
-    om_ptr.assign((size_t)S.ns + 1, 0);
-    std::vector<OEnt>& omap = H.omap;
-    omap.resize(ent.size());
-    {
-        std::vector<int32_t>& lidx = H.lidx;
-        std::vector<int32_t>& lst = H.lstamp;
-        lidx.resize((size_t)n);
-        lst.assign((size_t)n, -1);
-        size_t o = 0;
-        for (int32_t s = 0; s < S.ns; ++s) {
-            const int32_t c0 = S.sn_c0[(size_t)s], c1 = S.sn_c0[(size_t)s + 1], k = c1 - c0;
-            for (int64_t t = S.sn_rows_ptr[(size_t)s]; t < S.sn_rows_ptr[(size_t)s + 1]; ++t) {
-                lidx[(size_t)S.sn_rows[(size_t)t]] = k + (int32_t)(t - S.sn_rows_ptr[(size_t)s]);
-                lst[(size_t)S.sn_rows[(size_t)t]] = s;
-            }
-            om_ptr[(size_t)s] = (int64_t)o;
-            for (int32_t cpos = c0; cpos < c1; ++cpos)
-                for (int64_t e = colptr[(size_t)cpos]; e < colptr[(size_t)cpos + 1]; ++e) {
-                    const CholHost::Blk& b = ent[(size_t)e];
-                    int32_t a;
-                    if (b.row < c1) a = b.row - c0;
-                    else if (lst[(size_t)b.row] == s) a = lidx[(size_t)b.row];
-                    else return DPG_ERR_NUMERIC;   // the block is outside its front: bad analysis
-                    omap[o++] = OEnt{b.u, (int16_t)a, (int16_t)(cpos - c0), b.tr, 0};
-                }
-        }
-        om_ptr[(size_t)S.ns] = (int64_t)o;
-    }
-#ifdef DPG_PLAN_VERIFY
-    {   // the straightforward construction (binary search per block, per-front sort) must agree
-        std::vector<OEnt> ref;
-        for (int32_t s = 0; s < S.ns; ++s) {
-            const int32_t c0 = S.sn_c0[(size_t)s], k = S.sn_c0[(size_t)s + 1] - c0;
-            auto li = [&](int32_t p) -> int32_t {
-                if (p >= c0 && p < c0 + k) return p - c0;
-                const int32_t* b = S.sn_rows.data() + S.sn_rows_ptr[(size_t)s];
-                const int32_t* e = S.sn_rows.data() + S.sn_rows_ptr[(size_t)s + 1];
-                const int32_t* it = std::lower_bound(b, e, p);
-                return (it == e || *it != p) ? -1 : k + (int32_t)(it - b);
-            };
-            const size_t r0 = ref.size();
-            for (int64_t v = 0; v < n; ++v)
-                if (S.sn_of[(size_t)S.pos[(size_t)v]] == s) {
-                    const int32_t l = li(S.pos[(size_t)v]);
-                    ref.push_back(OEnt{(int32_t)v, (int16_t)l, (int16_t)l, 0, 0});
-                }
-            for (int64_t q = 0; q < n_pairs; ++q) {
-                const int32_t plo = S.pos[(size_t)pair_lo[q]], phi = S.pos[(size_t)pair_hi[q]];
-                if (S.sn_of[(size_t)std::min(plo, phi)] != s) continue;
-                ref.push_back(OEnt{(int32_t)(n + q), (int16_t)li(std::max(plo, phi)), (int16_t)li(std::min(plo, phi)),
-                                   plo > phi ? 0 : 1, 0});
-            }
-            std::sort(ref.begin() + r0, ref.end(), [](const OEnt& x, const OEnt& y) { return x.b != y.b ? x.b < y.b : x.a < y.a; });
-            if ((int64_t)r0 != om_ptr[(size_t)s]) { fprintf(stderr, "omap ptr mismatch at front %d\n", s); abort(); }
-        }
-        for (size_t i = 0; i < ref.size(); ++i)
-            if (ref[i].u != omap[i].u || ref[i].a != omap[i].a || ref[i].b != omap[i].b || ref[i].tr != omap[i].tr) {
-                fprintf(stderr, "omap mismatch at %zu\n", i);
-                abort();
-            }
-    }
-#endif
-    PLAN_T(2);
-    std::vector<SnDev>& sns = H.sns;
-    sns.resize((size_t)S.ns);
-    int64_t& acc_total = H.acc_total;
-    acc_total = 0;
-    for (int32_t s = 0; s < S.ns; ++s) {
-        SnDev& d = sns[(size_t)s];
-        d.c0 = S.sn_c0[(size_t)s];
-        d.k = S.sn_c0[(size_t)s + 1] - d.c0;
-        d.r = (int32_t)(S.sn_rows_ptr[(size_t)s + 1] - S.sn_rows_ptr[(size_t)s]);
-        d.nchild = (int32_t)(S.child_ptr[(size_t)s + 1] - S.child_ptr[(size_t)s]);
-        d.front_off = S.front_off[(size_t)s];
-        d.rows_off = S.sn_rows_ptr[(size_t)s];
-        d.child_off = S.child_ptr[(size_t)s];
-        d.omap_off = om_ptr[(size_t)s];
-        d.omap_n = (int32_t)(om_ptr[(size_t)s + 1] - om_ptr[(size_t)s]);
-        d.acc_off = acc_total;
-        d.parent = S.sn_parent[(size_t)s];
-        const int32_t m3 = 3 * (d.k + d.r);
-        d.G = (m3 <= kSmall && d.nchild <= kMaxCh)
-                  ? 1
-                  : std::min(kGmax, (3 * d.k + kFNB - 1) / kFNB + (3 * d.r + kFNB - 1) / kFNB);
-        d.need = 0;
-        acc_total += 3 * d.r;
-    }
-    for (int32_t s = 0; s < S.ns; ++s)
-        if (sns[(size_t)s].parent >= 0) sns[(size_t)sns[(size_t)s].parent].need += sns[(size_t)s].G;
-    if (c->track) {
-        c->cur_G.resize((size_t)S.ns);
-        for (int32_t s = 0; s < S.ns; ++s) c->cur_G[(size_t)s] = sns[(size_t)s].G;
-    }
-    // L11^-1 of the fronts with at least solve_inv_cols pivot columns (and at most 64 kInvMaxQ = 192)
-    H.inv_t.clear();
-    c->linv_total = 0;
-    c->lds_inv = 0;
-    for (int32_t s = 0; s < S.ns; ++s) {
-        SnDev& d = sns[(size_t)s];
-        const int32_t k3 = 3 * d.k;
-        d.inv = -1;
-        if (c->opts.solve_inv_cols <= 0 || k3 < c->opts.solve_inv_cols || k3 > 64 * kInvMaxQ ||
-            c->linv_total + (int64_t)k3 * k3 > INT32_MAX)
-            continue;
-        d.inv = (int32_t)c->linv_total;
-        c->linv_total += (int64_t)k3 * k3;
-        for (int32_t j0 = 0; j0 < k3; j0 += kInvCols) H.inv_t.push_back(make_int2(s, j0));
-    }
-    c->n_inv_tasks = (int64_t)H.inv_t.size();
-    std::vector<SolveSeg>& segs = H.segs;
-    segs.clear();
-    for (int32_t s = 0; s < S.ns; ++s) {
-        SnDev& d = sns[(size_t)s];
-        d.seg_off = (int32_t)segs.size();
-        const int32_t* rw = S.sn_rows.data() + d.rows_off;
-        for (int32_t t = 0; t < d.r;) {
-            const int32_t a = S.sn_of[(size_t)rw[t]];
-            int32_t t1 = t + 1;
-            while (t1 < d.r && S.sn_of[(size_t)rw[t1]] == a) ++t1;
-            segs.push_back(SolveSeg{a, t, t1, 0});
-            t = t1;
-        }
-        d.seg_n = (int32_t)segs.size() - d.seg_off;
-    }
-    // large fronts: per tile, the H blocks (omap range) and the children's column ranges
-    PLAN_T(3);
-    std::vector<FTask>& ftasks = H.ftasks;
-    std::vector<FChild>& fchild = H.fchild;
-    ftasks.clear();
-    fchild.clear();
-    for (int32_t s = 0; s < S.ns; ++s) {
-        SnDev& d = sns[(size_t)s];
-        d.ftask = (int32_t)ftasks.size();
-        const int32_t k3 = 3 * d.k, m3 = 3 * (d.k + d.r);
-        if (d.G == 1 && m3 <= kSmall && d.nchild <= kMaxCh) continue;
-        const OEnt* ob = omap.data() + d.omap_off;
-        std::vector<int32_t>& cuts = H.cuts;
-        cuts.clear();
-        for (int32_t c = 0; c < k3; c += kFNB) cuts.push_back(c);
-        for (int32_t c = k3; c < m3; c += kFNB) cuts.push_back(c);
-        cuts.push_back(m3);
-        // the children's column ranges per tile, tile-major and child order within a tile: each
-        // child visits only the tiles its rows reach (its rows map to increasing front rows, so
-        // the tiles' boundaries fall at increasing j), counted, then placed
-        const int32_t nt = (int32_t)cuts.size() - 1;
-        std::vector<int32_t>& tcnt = H.tcnt;
-        tcnt.assign((size_t)nt + 1, 0);
-        const int64_t ch0 = S.child_ptr[(size_t)s], ch1 = S.child_ptr[(size_t)s + 1];
-        // the tile holding front row c: [0, k3) in kFNB steps, then [k3, m3) in kFNB steps
-        const int32_t nt_k = (k3 + kFNB - 1) / kFNB;
-        auto tile_of = [&](int32_t c) { return c < k3 ? c / kFNB : nt_k + (c - k3) / kFNB; };
-        for (int64_t ci = ch0; ci < ch1; ++ci) {
-            const SnDev& cd = sns[(size_t)S.child_list[(size_t)ci]];
-            if (cd.r == 0) continue;
-            const int32_t* rm = S.relmap.data() + cd.rows_off;
-            const int32_t ta = tile_of(3 * rm[0]), tb = tile_of(3 * rm[cd.r - 1] + 2);
-            for (int32_t t = ta; t <= tb; ++t) tcnt[(size_t)t + 1]++;   // an upper bound: empty ranges drop below
-        }
-        const size_t base = fchild.size();
-        for (int32_t t = 0; t < nt; ++t) tcnt[(size_t)t + 1] += tcnt[(size_t)t];
-        fchild.resize(base + (size_t)tcnt[(size_t)nt]);
-        std::vector<int32_t>& tfill = H.tfill;
-        tfill.assign(tcnt.begin(), tcnt.end() - 1);
-        std::vector<char>& used = H.tused;
-        used.assign(fchild.size() - base, 0);
-        for (int64_t ci = ch0; ci < ch1; ++ci) {
-            const SnDev& cd = sns[(size_t)S.child_list[(size_t)ci]];
-            if (cd.r == 0) continue;
-            const int32_t* rm = S.relmap.data() + cd.rows_off;
-            const int32_t ta = tile_of(3 * rm[0]), tb = tile_of(3 * rm[cd.r - 1] + 2);
-            int32_t ja = first_at_or_after(rm, cd.r, cuts[(size_t)ta]);
-            for (int32_t t = ta; t <= tb; ++t) {
-                const int32_t jb = first_at_or_after(rm, cd.r, cuts[(size_t)t + 1]);
-                const size_t at = (size_t)tfill[(size_t)t]++;
-                if (jb > ja) {
-                    fchild[base + at] = FChild{ja, jb, cd.k, cd.r, cd.front_off, cd.rows_off};
-                    used[at] = 1;
-                }
-                ja = jb;
-            }
-        }
-        // compact (a child whose rows skip a whole tile left an unused slot there)
-        size_t w = base;
-        for (int32_t t = 0; t < nt; ++t) {
-            const int32_t c0 = cuts[(size_t)t], c1 = cuts[(size_t)t + 1];
-            FTask ft{0, 0, (int32_t)w, 0};
-            ft.om_b = (int32_t)d.omap_off + (int32_t)(std::lower_bound(ob, ob + d.omap_n, c0 / 3,
-                          [](const OEnt& o, int32_t v) { return o.b < v; }) - ob);
-            ft.om_e = (int32_t)d.omap_off + (int32_t)(std::upper_bound(ob, ob + d.omap_n, (c1 - 1) / 3,
-                          [](int32_t v, const OEnt& o) { return v < o.b; }) - ob);
-            for (int32_t a = tcnt[(size_t)t]; a < tcnt[(size_t)t + 1]; ++a)
-                if (used[(size_t)a]) fchild[w++] = fchild[base + (size_t)a];
-            ft.ch_cnt = (int32_t)w - ft.ch_off;
-            ftasks.push_back(ft);
-        }
-        fchild.resize(w);
-    }
-    // fused tickets (front * 64 + team member) in critical-path order: a front's priority is its
-    // estimated time plus its parent's priority (the longest remaining path to the root), so
-    // sorting by descending priority is topological (children first) and starts the long chains
-    // before the bulk of the leaves
-#ifdef DPG_PLAN_VERIFY
-    {   // the child column ranges by a linear scan must agree
-        size_t fi = 0;
-        for (int32_t s = 0; s < S.ns; ++s) {
-            const SnDev& d = sns[(size_t)s];
-            const int32_t k3 = 3 * d.k, m3 = 3 * (d.k + d.r);
-            if (d.G == 1 && m3 <= kSmall && d.nchild <= kMaxCh) continue;
-            std::vector<int32_t> cu;
-            for (int32_t c = 0; c < k3; c += kFNB) cu.push_back(c);
-            for (int32_t c = k3; c < m3; c += kFNB) cu.push_back(c);
-            cu.push_back(m3);
-            for (size_t t = 0; t + 1 < cu.size(); ++t)
-                for (int64_t ci = S.child_ptr[(size_t)s]; ci < S.child_ptr[(size_t)s + 1]; ++ci) {
-                    const SnDev& cd = sns[(size_t)S.child_list[(size_t)ci]];
-                    const int32_t* rm = S.relmap.data() + cd.rows_off;
-                    int32_t ja = 3 * cd.r, jb = 0;
-                    for (int32_t j = 0; j < 3 * cd.r; ++j) {
-                        const int32_t pj = 3 * rm[j / 3] + j % 3;
-                        if (pj >= cu[t] && pj < cu[t + 1]) { ja = std::min(ja, j); jb = j + 1; }
-                    }
-                    if (jb > ja) {
-                        if (fi >= fchild.size() || fchild[fi].ja != ja || fchild[fi].jb != jb) {
-                            fprintf(stderr, "fchild mismatch at %zu\n", fi);
-                            abort();
-                        }
-                        ++fi;
-                    }
-                }
-        }
-        if (fi != fchild.size()) { fprintf(stderr, "fchild count mismatch\n"); abort(); }
-    }
-#endif
-    PLAN_T(4);
-    std::vector<double>& prio = H.prio;
-    prio.assign((size_t)S.ns, 0.0);
-    for (int32_t s = S.ns - 1; s >= 0; --s) {
-        const SnDev& d = sns[(size_t)s];
-        const int32_t m3 = 3 * (d.k + d.r);
-        // (us, fitted to tools/chol_bench_t's per-front log: a small front's time grows with its
-        // columns -- ~0.9 us each for the in-LDS factorization -- as well as its rows)
-        const double est = d.G == 1 ? 4.0 + 0.06 * m3 + 0.9 * (3 * d.k) : 10.0 + 20.0 * ((3 * d.k + kFNB - 1) / kFNB);
-        prio[(size_t)s] = est + (d.parent >= 0 ? prio[(size_t)d.parent] : 0.0);
-    }
-    // (descending priority, ties in level-list order)
-    std::vector<std::pair<double, int32_t>>& key = H.key;
-    key.resize((size_t)S.ns);
-    for (int32_t i = 0; i < S.ns; ++i) key[(size_t)i] = {-prio[(size_t)S.level_list[(size_t)i]], i};
-    std::sort(key.begin(), key.end());
-    std::vector<int32_t>& fo = H.fo;
-    fo.resize((size_t)S.ns);
-    for (int32_t i = 0; i < S.ns; ++i) fo[(size_t)i] = S.level_list[(size_t)key[(size_t)i].second];
-#ifdef DPG_PLAN_VERIFY
-    {
-        std::vector<int32_t> ref(S.level_list.begin(), S.level_list.end());
-        std::stable_sort(ref.begin(), ref.end(), [&](int32_t a, int32_t b) { return prio[(size_t)a] > prio[(size_t)b]; });
-        if (ref != fo) { fprintf(stderr, "front order mismatch\n"); abort(); }
-    }
-#endif
-    std::vector<int32_t>& order_fac = H.order_fac;
-    order_fac.clear();
-    for (int32_t s : fo)
-        for (int32_t m = 0; m < sns[(size_t)s].G; ++m) order_fac.push_back(s * 64 + m);
-    c->n_tickets = (int64_t)order_fac.size();
-    PLAN_T(5);
-    c->level_ptr = S.level_ptr;
-    // assembly tiles of front s, `ct` columns each: the omap range and the children (with their
-    // contiguous column range) that land in the tile
-    auto build_tiles = [&](int32_t s, int32_t ct, std::vector<AsmTask>& tl, std::vector<AsmChild>& cl) {
-        const SnDev& d = sns[(size_t)s];
-        const int32_t m3 = 3 * (d.k + d.r);
-        const OEnt* ob = omap.data() + d.omap_off;
-        for (int32_t c0 = 0; c0 < m3; c0 += ct) {
-            const int32_t c1 = std::min(c0 + ct, m3);
-            AsmTask t{s, c0, 0, 0, (int32_t)cl.size(), 0};
-            // omap entries with block column in [c0 / 3, (c1 - 1) / 3]
-            t.om_b = (int32_t)d.omap_off + (int32_t)(std::lower_bound(ob, ob + d.omap_n, c0 / 3,
-                         [](const OEnt& o, int32_t v) { return o.b < v; }) - ob);
-            t.om_e = (int32_t)d.omap_off + (int32_t)(std::upper_bound(ob, ob + d.omap_n, (c1 - 1) / 3,
-                         [](int32_t v, const OEnt& o) { return v < o.b; }) - ob);
-            for (int64_t ci = S.child_ptr[(size_t)s]; ci < S.child_ptr[(size_t)s + 1]; ++ci) {
-                const int32_t ch = S.child_list[(size_t)ci];
-                const SnDev& cd = sns[(size_t)ch];
-                const int32_t ja = first_at_or_after(S.relmap.data() + cd.rows_off, cd.r, c0);
-                const int32_t jb = first_at_or_after(S.relmap.data() + cd.rows_off, cd.r, c1);
-                if (jb > ja) cl.push_back(AsmChild{ch, ja, jb, 0});
-            }
-            t.ch_cnt = (int32_t)cl.size() - t.ch_off;
-            tl.push_back(t);
-        }
-    };
-    // fused path: LDS budget of the largest front
-    for (int32_t s = 0; s < S.ns; ++s) {
-        const SnDev& d = sns[(size_t)s];
-        c->lds_fused = std::max(c->lds_fused, 8 * fused_lds_doubles(3 * (d.k + d.r), 3 * d.k, true));
-    }
-    // two panel buffers for the chain when every front fits, else one (the chain step goes through HBM)
-    c->fused_db = c->lds_fused <= 160 * 1024;
-    if (!c->fused_db) {
-        c->lds_fused = 0;
-        for (int32_t s = 0; s < S.ns; ++s) {
-            const SnDev& d = sns[(size_t)s];
-            c->lds_fused = std::max(c->lds_fused, 8 * fused_lds_doubles(3 * (d.k + d.r), 3 * d.k, false));
-        }
-    }
-    c->fused = c->lds_fused <= 160 * 1024 && c->opts.fused;
-    // LDS of the DAG solves: the largest front
-    // the solves' LDS: diagonal block D + staging region R + reciprocals + right-hand side / gathered
-    // x + row positions.  Their VGPR budget (the 64-step chains) already holds them to two
-    // workgroups per CU, so R defaults to what fills 80 KB; opts.solve_stage overrides it (doubles,
-    // 0 = no staging)
-    size_t lds_rest = 0;
-    for (int32_t s = 0; s < S.ns; ++s) {
-        const int32_t m3 = 3 * (sns[(size_t)s].k + sns[(size_t)s].r);
-        lds_rest = std::max(lds_rest, (size_t)(kSB * kDL + kSB + m3 + 2 + m3 / 6 + 2 + 2 * kMaxSeg) * sizeof(double));
-    }
-    {
-        const long room = (long)(80 * 1024) - (long)lds_rest;
-        const long want = c->opts.solve_stage >= 0 ? (long)c->opts.solve_stage : room / (long)sizeof(double);
-        const long cap = ((long)(160 * 1024) - (long)lds_rest) / (long)sizeof(double);
-        c->solve_stage = (int32_t)std::max<long>(0, std::min<long>(want, cap)) & ~1;
-        // tests: 0 = every front takes the parent path
-        c->solve_maxseg = c->opts.solve_maxseg >= 0 ? std::min(c->opts.solve_maxseg, kMaxSeg) : kMaxSeg;
-    }
-    c->lds_solve_max = (size_t)c->solve_stage * sizeof(double) + lds_rest;
-    if (c->lds_solve_max > 160 * 1024) return DPG_ERR_SIZE;
-    std::vector<AsmTask>& asm_t = H.asm_t;
-    std::vector<AsmChild>& asm_c = H.asm_c;
-    std::vector<int2>& panel_t = H.panel_t;
-    std::vector<int4>& upd_t = H.upd_t;
-    asm_t.clear();
-    asm_c.clear();
-    panel_t.clear();
-    upd_t.clear();
-    c->plan.clear();
-    if (!c->fused) {
-        // level-synchronous path: per level, assembly tiles, then panel + update steps
-        c->plan.assign((size_t)S.n_levels, CholDev::Level{});
-        for (int32_t l = 0; l < S.n_levels; ++l) {
-            int32_t maxk3 = 0;
-            CholDev::Level& L = c->plan[(size_t)l];
-            L.asm_off = (int32_t)asm_t.size();
-            L.lds_asm = 0;
-            for (int32_t q = S.level_ptr[(size_t)l]; q < S.level_ptr[(size_t)l + 1]; ++q) {
-                const int32_t s = S.level_list[(size_t)q];
-                const SnDev& d = sns[(size_t)s];
-                const int32_t m3 = 3 * (d.k + d.r);
-                L.lds_asm = std::max(L.lds_asm, (size_t)kCT * m3 * sizeof(double));
-                maxk3 = std::max(maxk3, 3 * d.k);
-                build_tiles(s, kCT, asm_t, asm_c);
-            }
-            L.asm_cnt = (int32_t)asm_t.size() - L.asm_off;
-            c->n_launches += 1;
-            for (int32_t j0 = 0; j0 < maxk3; j0 += kNB) {
-                CholDev::Step st{(int32_t)panel_t.size(), 0, 1, 0, (int32_t)upd_t.size(), 0};
-                int32_t maxR = 0;
-                for (int32_t q = S.level_ptr[(size_t)l]; q < S.level_ptr[(size_t)l + 1]; ++q) {
-                    const int32_t s = S.level_list[(size_t)q];
-                    const SnDev& d = sns[(size_t)s];
-                    const int32_t m3 = 3 * (d.k + d.r), k3 = 3 * d.k;
-                    if (k3 <= j0) continue;
-                    panel_t.push_back(make_int2(s, j0));
-                    maxR = std::max(maxR, m3 - j0);
-                    const int32_t base = j0 + std::min(kNB, k3 - j0), nt = (m3 - base + kUT - 1) / kUT;
-                    for (int32_t ti = 0; ti < nt; ++ti)
-                        for (int32_t tl = 0; tl <= ti; ++tl) upd_t.push_back(make_int4(s, j0, base + kUT * ti, base + kUT * tl));
-                }
-                st.panel_cnt = (int32_t)panel_t.size() - st.panel_off;
-                st.upd_cnt = (int32_t)upd_t.size() - st.upd_off;
-                st.max_rows = maxR;
-                st.rpt = maxR <= kT ? 1 : maxR <= 2 * kT ? 2 : maxR <= 4 * kT ? 4 : 0;
-                if (st.rpt == 0) return DPG_ERR_SIZE;
-                L.steps.push_back(st);
-                c->n_launches += 1 + (st.upd_cnt > 0);
-            }
-            if (L.lds_asm > 160 * 1024) return DPG_ERR_SIZE;
-        }
-    }
-    // solves: the forward solve runs in the factorization's critical-path order (children first);
-    // the backward solve by descending height -- the estimated time of the longest path from a
-    // front DOWN to a leaf, which exceeds every child's, so the order is topological (parents
-    // first) and the deepest chain is claimed first (the reverse of the forward order claimed the
-    // fronts near the root first, whatever hangs below them: a chain front could be claimed
-    // microseconds after its parent finished)
-    PLAN_T(6);
-    {
-        std::vector<double>& hgt = H.hgt;
-        hgt.assign((size_t)S.ns, 0.0);
-        for (int32_t s = 0; s < S.ns; ++s) {   // children precede parents in supernode order
-            const SnDev& d = sns[(size_t)s];
-            hgt[(size_t)s] += 2.0 + 0.01 * (3 * (d.k + d.r)) + 0.05 * (3 * d.k);   // us, tools/chol_bench_t
-            if (d.parent >= 0) hgt[(size_t)d.parent] = std::max(hgt[(size_t)d.parent], hgt[(size_t)s]);
-        }
-        // counting sort by height in 0.25 us buckets, descending; inside a bucket by descending
-        // supernode index, so a parent (higher index, greater height) still precedes its children
-        std::vector<int32_t>& cnt = H.hcnt;
-        double hmax = 0.0;
-        for (int32_t s = 0; s < S.ns; ++s) hmax = std::max(hmax, hgt[(size_t)s]);
-        const int32_t nb = (int32_t)(hmax * 4.0) + 2;
-        cnt.assign((size_t)nb + 1, 0);
-        for (int32_t s = 0; s < S.ns; ++s) ++cnt[(size_t)(nb - 1 - (int32_t)(hgt[(size_t)s] * 4.0)) + 1];
-        for (int32_t b = 0; b < nb; ++b) cnt[(size_t)b + 1] += cnt[(size_t)b];
-        H.bwd.resize((size_t)S.ns);
-        for (int32_t s = S.ns - 1; s >= 0; --s)
-            H.bwd[(size_t)cnt[(size_t)(nb - 1 - (int32_t)(hgt[(size_t)s] * 4.0))]++] = s;
-    }
-    // [ticket | children-done counters [ns] | panel flags [ns] | backward: ticket | done [ns] |
-    //  pivot-tile hand-off flags [per large-front tile]]
-    c->sync_bytes = ((size_t)(2 + 3 * S.ns + ftasks.size()) * sizeof(int32_t) + 15) & ~size_t(15);
-    H.dblocks.clear();
-    for (int32_t s = 0; s < S.ns; ++s)
-        for (int32_t jb = 0; jb < 3 * sns[(size_t)s].k; jb += kSB) H.dblocks.push_back(make_int2(s, jb));
-    c->n_dblocks = (int64_t)H.dblocks.size();
-    // measured (tools/r3_gn_job.sh, profiles/r03): the inversion launch (~55 us at config 4) costs
-    // more than the chains it removes from the solves (re-solve 0.250 -> 0.241 ms), so the chains
-    // stay the default; opts.solve_dinv selects the inverted blocks
-    c->use_dinv = c->opts.solve_dinv != 0;
-    PLAN_T(7);
-    return DPG_OK;
-}
-
 // The structure arrays are packed into one pinned staging buffer and go up in ONE asynchronous
 // copy into one device arena (the pointers of c point into it); one synchronisation at the end.
-int chol_upload(CholDev* c, int64_t n, const CholHost& H) {
+int chol_upload(CholDev* c) {
     const dpg_chol_sym& S = c->sym;
+    const CholPlan& H = c->plan;
+    const int64_t n = H.n;
     ++c->build_gen;   // (the selected inverse's lists follow the analysis: rebuilt on its next request)
     c->has_factor = false;
     auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
@@ -2922,7 +2320,7 @@ int chol_upload(CholDev* c, int64_t n, const CholHost& H) {
     add(&c->segs, H.segs);
     add(&c->dblocks, H.dblocks);
     add(&c->inv_tasks, H.inv_t);
-    if (!c->fused) {
+    if (!H.fused) {
         add(&c->asm_tasks, H.asm_t);
         add(&c->asm_child, H.asm_c);
         add(&c->panel_tasks, H.panel_t);
@@ -2956,7 +2354,7 @@ int chol_upload(CholDev* c, int64_t n, const CholHost& H) {
     // a re-allocated front, y or pending-update buffer has lost the tracked factorization (a new
     // allocation may come back at the old address: the capacities tell)
     const size_t cap0[3] = {c->c_fronts, c->c_acc, c->c_ysol};
-    rc |= dreserve(&c->sync, &c->c_sync, c->sync_bytes / sizeof(int32_t));
+    rc |= dreserve(&c->sync, &c->c_sync, H.sync_bytes / sizeof(int32_t));
     rc |= dreserve(&c->fronts, &c->c_fronts, (size_t)S.front_off[(size_t)S.ns]);
     rc |= dreserve(&c->acc, &c->c_acc, (size_t)H.acc_total);
     rc |= dreserve(&c->ysol, &c->c_ysol, (size_t)(3 * n));
@@ -2964,29 +2362,24 @@ int chol_upload(CholDev* c, int64_t n, const CholHost& H) {
     rc |= dreserve(&c->xsol, &c->c_xsol, (size_t)(3 * n));
     rc |= dreserve(&c->status, &c->c_status, 1);
     rc |= dreserve(&c->dinv, &c->c_dinv, (size_t)(3 * n) * kSB);
-    rc |= dreserve(&c->linv, &c->c_linv, (size_t)std::max<int64_t>(c->linv_total, 1));
+    rc |= dreserve(&c->linv, &c->c_linv, (size_t)std::max<int64_t>(H.linv_total, 1));
     if (!rc) rc |= hipMemsetAsync(c->status, 0, sizeof(int32_t), nullptr) != hipSuccess;
     // the staging buffer is reused by the next build: wait for the copy (always, even after an error)
     rc |= hipStreamSynchronize(nullptr) != hipSuccess;
     return rc ? DPG_ERR_HIP : DPG_OK;
 }
 
-// the host structures of c's build in progress (a plan and its upload may be split:
-// dpg_chol_create_sym_plan / _upload, possibly on two threads one after the other)
-CholHost& build_host(CholDev* c) {
-    if (!c->host) c->host = new CholHost();
-    return *static_cast<CholHost*>(c->host);
-}
-void free_host(void* p) { delete static_cast<CholHost*>(p); }
+// (a plan and its upload may be split: dpg_chol_create_sym_plan / _upload, possibly on two threads
+// one after the other)
 int chol_build_plan(CholDev* c, int64_t n, const int32_t* pair_lo, const int32_t* pair_hi, int64_t n_pairs) {
     const double t_b0 = wall_ms();
-    const int rc = chol_plan(c, n, pair_lo, pair_hi, n_pairs, build_host(c));
+    const int rc = dpg_chol_plan_build(c->plan, c->sym, c->opts, c->track, n, pair_lo, pair_hi, n_pairs);
     c->t_build[0] = wall_ms() - t_b0;
     return rc;
 }
 int chol_build_upload(CholDev* c) {
     const double t_b1 = wall_ms();
-    const int rc = chol_upload(c, c->n, build_host(c));
+    const int rc = chol_upload(c);
     c->t_build[1] = wall_ms() - t_b1;
     return rc;
 }
@@ -3008,7 +2401,7 @@ int dpg_chol_create_sym_plan(void** h, int64_t n, const int32_t* pair_lo, const 
     *h = c;
     return DPG_OK;
 }
-// chol_plan's first part ahead of the plan (pos / perm: the ordering the plan's analysis will
+// the plan's first stage ahead of the plan (pos / perm: the ordering the plan's analysis will
 // carry); creates the solver object when *h is NULL.  Host only; not concurrently with a plan or an
 // upload of the same object.
 int dpg_chol_plan_blocks(void** h, int64_t n, const int32_t* pos, const int32_t* perm, const int32_t* pair_lo,
@@ -3016,16 +2409,13 @@ int dpg_chol_plan_blocks(void** h, int64_t n, const int32_t* pos, const int32_t*
     if (!h || n <= 0 || !pos || !perm || n_pairs < 0 || (n_pairs > 0 && (!pair_lo || !pair_hi))) return DPG_ERR_ARG;
     CholDev* c = *h ? reinterpret_cast<CholDev*>(*h) : new CholDev();
     *h = c;
-    CholHost& H = build_host(c);
-    H.blocks_ready = false;
-    plan_blocks(H, n, pos, perm, pair_lo, pair_hi, n_pairs);
-    H.blocks_ready = true;
+    dpg_chol_plan_prebucket(c->plan, n, pos, perm, pair_lo, pair_hi, n_pairs);
     return DPG_OK;
 }
 // drop prebuilt H-block buckets (their ordering was not the one the next plan will carry: the
 // derivation they were built beside failed)
 void dpg_chol_blocks_invalidate(void* h) {
-    if (h) build_host(reinterpret_cast<CholDev*>(h)).blocks_ready = false;
+    if (h) reinterpret_cast<CholDev*>(h)->plan.blocks_ready = false;
 }
 int dpg_chol_create_sym_upload(void** h) {
     CholDev* c = reinterpret_cast<CholDev*>(*h);
@@ -3035,25 +2425,7 @@ int dpg_chol_create_sym_upload(void** h) {
     return rc;
 }
 
-#ifdef DPG_PLAN_TIMING
-double dpg_plan_t_export[8];
-#endif
-// host half of a build alone (no device calls), for CPU timing of the incremental rebuild
-int dpg_chol_plan_host(int64_t n, const int32_t* pair_lo, const int32_t* pair_hi, int64_t n_pairs,
-                       const dpg_chol_sym* S, double* ms) {
-    thread_local CholHost H;
-    thread_local CholDev c;
-    c.sym = *S;
-    const double t0 = wall_ms();
-    const int rc = chol_plan(&c, n, pair_lo, pair_hi, n_pairs, H);
-    if (ms) *ms = wall_ms() - t0;
-#ifdef DPG_PLAN_TIMING
-    for (int k = 0; k < 8; ++k) dpg_plan_t_export[k] = g_plan_t[k];
-#endif
-    return rc;
-}
-
-int dpg_chol_fused(void* h) { return h && reinterpret_cast<const CholDev*>(h)->fused ? 1 : 0; }
+int dpg_chol_fused(void* h) { return h && reinterpret_cast<const CholDev*>(h)->plan.fused ? 1 : 0; }
 
 void dpg_chol_build_times(void* h, double out[2]) {
     const CholDev* c = reinterpret_cast<const CholDev*>(h);
@@ -3061,12 +2433,83 @@ void dpg_chol_build_times(void* h, double out[2]) {
     out[1] = c ? c->t_build[1] : 0.0;
 }
 
+// ---- one launch site per solver kernel ----
+// The sync words of one solve (plan.sync_bytes, zeroed before the factorization, or before the
+// forward solve where it runs alone), ns = the number of fronts:
+//   [0]                    ticket of the factorization / the forward solve
+//   [1, 1 + ns)            children-done counters of the same
+//   [1 + ns, 1 + 2 ns)     panel flags of the large fronts
+//   [1 + 2 ns]             ticket of the backward solve
+//   [2 + 2 ns, 2 + 3 ns)   its done flags
+//   [2 + 3 ns, ..)         pivot-tile hand-off flags, one per large-front tile
+// Each kernel takes the base of its part (chol_factor_dag the whole array), and these helpers are
+// the only places that know the offsets.  The level path's backward solve used to take its part at
+// 1 + ns -- inside the panel flags, which that path never uses; it now takes 1 + 2 ns like every
+// other caller: the only launch argument that differs from the hand-written launches these
+// helpers replaced.
+//
+// gate: the pipelined loop's (gate_off); keep: the partial refactorization's per-front flags; di /
+// li: inverted diagonal blocks / L11^-1 for the solves' diagonal part; X, max_out: the backward
+// solve retracts the poses as it goes.
+
+// fused factorization + forward solve of hb's system (its right-hand side follows its blocks)
+static void launch_factor(CholDev* c, hipStream_t st, const double* hb, const int32_t* gate, const uint8_t* keep) {
+    const CholPlan& P = c->plan;
+    hipLaunchKernelGGL(chol_factor_dag, dim3((unsigned)P.n_tickets), dim3(kFT), P.lds_fused, st, c->order_fac, c->sync,
+                       c->status, c->sns, c->omap, c->relmap, c->child_list, c->ftasks, c->fchild, hb, hb + 9 * P.nnzb_upper,
+                       c->perm, c->fronts, c->ysol, c->acc, c->sym.ns, P.fused_db ? 1 : 0, gate, keep);
+}
+
+static void launch_forward(CholDev* c, hipStream_t st, const double* hb, const double* di, const int32_t* gate,
+                           const double* li) {
+    const CholPlan& P = c->plan;
+    hipLaunchKernelGGL(chol_forward_dag, dim3(c->sym.ns), dim3(kT), P.lds_solve_max, st, c->order_fwd, c->sync, c->status,
+                       c->sns, c->child_list, c->relmap, c->fronts, hb + 9 * P.nnzb_upper, c->perm, c->ysol, c->acc,
+                       P.solve_stage, di, gate, li);
+}
+
+static void launch_backward(CholDev* c, hipStream_t st, const double* di, const int32_t* gate, double* X, double* max_out,
+                            const double* li) {
+    const CholPlan& P = c->plan;
+    const int32_t ns = c->sym.ns;
+    hipLaunchKernelGGL(chol_backward_dag, dim3(ns), dim3(kT), P.lds_solve_max, st, c->order_bwd, c->sync + 1 + 2 * ns,
+                       c->status, c->sns, c->rows, c->segs, c->fronts, c->ysol, c->xsol, P.solve_stage, P.solve_maxseg, di, gate,
+                       X ? c->perm : nullptr, X, max_out, li);
+}
+
+// the solves' inverted diagonal blocks from the fronts just factored (opts.solve_dinv); returns
+// what the solves take as `di`
+static const double* launch_inv_diag(CholDev* c, hipStream_t st) {
+    const CholPlan& P = c->plan;
+    if (P.use_dinv && P.n_dblocks > 0)
+        hipLaunchKernelGGL(chol_inv_diag, dim3((unsigned)P.n_dblocks), dim3(64), 0, st, c->dblocks, c->sns, c->fronts, c->dinv);
+    return P.use_dinv ? c->dinv : nullptr;
+}
+
 // L11^-1 of the large fronts from the fronts just factored (gate: the pipelined loop's, refactoring
 // iterations only)
 static void launch_inv(CholDev* c, hipStream_t st, const int32_t* gate) {
-    if (c->n_inv_tasks > 0)
-        hipLaunchKernelGGL(chol_inv_l11, dim3((unsigned)c->n_inv_tasks), dim3(kInvThreads), c->lds_inv, st, c->inv_tasks, c->sns,
+    const CholPlan& P = c->plan;
+    if (P.n_inv_tasks > 0)
+        hipLaunchKernelGGL(chol_inv_l11, dim3((unsigned)P.n_inv_tasks), dim3(kInvThreads), P.lds_inv, st, c->inv_tasks, c->sns,
                            c->fronts, c->linv, gate);
+}
+
+// the level-synchronous factorization: per level, assembly tiles, then panel + update steps
+static void launch_levels(CholDev* c, hipStream_t st, const double* hb) {
+    int pid = 0;
+    for (const CholPlan::Level& L : c->plan.levels) {
+        hipLaunchKernelGGL(chol_assemble, dim3(L.asm_cnt), dim3(kT), L.lds_asm, st, c->asm_tasks + L.asm_off,
+                           c->asm_child, c->sns, c->omap, hb, c->relmap, c->fronts, pid++);
+        for (const CholPlan::Step& p : L.steps) {
+            const Task2* pt = c->panel_tasks + p.panel_off;
+            if (p.rpt == 1) hipLaunchKernelGGL(chol_panel<kT>, dim3(p.panel_cnt), dim3(kT), 0, st, pt, c->sns, c->fronts, c->status, pid++);
+            else if (p.rpt == 2) hipLaunchKernelGGL(chol_panel<2 * kT>, dim3(p.panel_cnt), dim3(2 * kT), 0, st, pt, c->sns, c->fronts, c->status, pid++);
+            else hipLaunchKernelGGL(chol_panel<4 * kT>, dim3(p.panel_cnt), dim3(4 * kT), 0, st, pt, c->sns, c->fronts, c->status, pid++);
+            if (p.upd_cnt > 0)
+                hipLaunchKernelGGL(chol_update, dim3(p.upd_cnt), dim3(kT), 0, st, c->upd_tasks + p.upd_off, c->sns, c->fronts, pid++);
+        }
+    }
 }
 
 // the values in fronts now belong to the current analysis
@@ -3082,60 +2525,28 @@ static void note_factored(CholDev* c, int64_t refactored, int64_t kept, int64_t 
     c->fac_ysol = c->ysol;
     c->fac_acc = c->acc;
     c->sym_is_fac = true;
-    c->fac_db = c->fused_db;
+    c->fac_db = c->plan.fused_db;
 }
 
 extern "C" int dpg_chol_solve(void* h, const double* hb, void* stream) {
     CholDev* c = reinterpret_cast<CholDev*>(h);
+    const CholPlan& P = c->plan;
     note_factored(c, c->sym.ns, 0, 0);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const dpg_chol_sym& S = c->sym;
-    const double* g = hb + 9 * c->nnzb_upper;
     if (hipMemsetAsync(c->status, 0, sizeof(int32_t), st) != hipSuccess) return DPG_ERR_HIP;
-    if (c->fused) {
-        if (hipMemsetAsync(c->sync, 0, c->sync_bytes, st) != hipSuccess) return DPG_ERR_HIP;
-        hipLaunchKernelGGL(chol_factor_dag, dim3((unsigned)c->n_tickets), dim3(kFT), c->lds_fused, st, c->order_fac,
-                           c->sync, c->status, c->sns, c->omap, c->relmap, c->child_list, c->ftasks, c->fchild, hb, g,
-                           c->perm, c->fronts,
-                           c->ysol, c->acc, S.ns, c->fused_db ? 1 : 0, nullptr, nullptr);
-        if (c->use_dinv && c->n_dblocks > 0)
-            hipLaunchKernelGGL(chol_inv_diag, dim3((unsigned)c->n_dblocks), dim3(64), 0, st, c->dblocks, c->sns, c->fronts, c->dinv);
-        hipLaunchKernelGGL(chol_backward_dag, dim3(S.ns), dim3(kT), c->lds_solve_max, st, c->order_bwd,
-                           c->sync + 1 + 2 * S.ns, c->status, c->sns, c->rows, c->segs, c->fronts, c->ysol, c->xsol, c->solve_stage, c->solve_maxseg,
-                           c->use_dinv ? c->dinv : nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-        // the inverse after the backward (which, as a refactoring iteration of the gated loop, chains):
-        // the chord steps of dpg_chol_resolve then do the same arithmetic as the gated loop's
-        c->inv_valid = c->keep_inv && c->n_inv_tasks > 0;
-        if (c->inv_valid) launch_inv(c, st, nullptr);
-        return hipGetLastError() == hipSuccess ? DPG_OK : DPG_ERR_HIP;
+    if (P.fused) {
+        if (hipMemsetAsync(c->sync, 0, P.sync_bytes, st) != hipSuccess) return DPG_ERR_HIP;
+        launch_factor(c, st, hb, nullptr, nullptr);
+    } else {
+        launch_levels(c, st, hb);
+        if (hipMemsetAsync(c->sync, 0, P.sync_bytes, st) != hipSuccess) return DPG_ERR_HIP;
     }
-    int pid = 0;
-    for (int32_t l = 0; l < S.n_levels; ++l) {
-        const CholDev::Level& L = c->plan[(size_t)l];
-        hipLaunchKernelGGL(chol_assemble, dim3(L.asm_cnt), dim3(kT), L.lds_asm, st, c->asm_tasks + L.asm_off,
-                           c->asm_child, c->sns, c->omap, hb, c->relmap, c->fronts, pid++);
-        for (const CholDev::Step& p : L.steps) {
-            const int2* pt = c->panel_tasks + p.panel_off;
-            if (p.rpt == 1) hipLaunchKernelGGL(chol_panel<kT>, dim3(p.panel_cnt), dim3(kT), 0, st, pt, c->sns, c->fronts, c->status, pid++);
-            else if (p.rpt == 2) hipLaunchKernelGGL(chol_panel<2 * kT>, dim3(p.panel_cnt), dim3(2 * kT), 0, st, pt, c->sns, c->fronts, c->status, pid++);
-            else hipLaunchKernelGGL(chol_panel<4 * kT>, dim3(p.panel_cnt), dim3(4 * kT), 0, st, pt, c->sns, c->fronts, c->status, pid++);
-            if (p.upd_cnt > 0)
-                hipLaunchKernelGGL(chol_update, dim3(p.upd_cnt), dim3(kT), 0, st, c->upd_tasks + p.upd_off, c->sns, c->fronts, pid++);
-        }
-    }
-    if (hipMemsetAsync(c->sync, 0, c->sync_bytes, st) != hipSuccess) return DPG_ERR_HIP;
-    int32_t* sync_f = c->sync;
-    int32_t* sync_b = c->sync + 1 + S.ns;
-    if (c->use_dinv && c->n_dblocks > 0)
-        hipLaunchKernelGGL(chol_inv_diag, dim3((unsigned)c->n_dblocks), dim3(64), 0, st, c->dblocks, c->sns, c->fronts, c->dinv);
-    const double* di = c->use_dinv ? c->dinv : nullptr;
-    hipLaunchKernelGGL(chol_forward_dag, dim3(S.ns), dim3(kT), c->lds_solve_max, st, c->order_fwd, sync_f, c->status,
-                       c->sns, c->child_list, c->relmap, c->fronts, g, c->perm, c->ysol, c->acc, c->solve_stage, di, nullptr,
-                       nullptr);
-    hipLaunchKernelGGL(chol_backward_dag, dim3(S.ns), dim3(kT), c->lds_solve_max, st, c->order_bwd, sync_b, c->status,
-                       c->sns, c->rows, c->segs, c->fronts, c->ysol, c->xsol, c->solve_stage, c->solve_maxseg, di, nullptr, nullptr,
-                       nullptr, nullptr, nullptr);
-    c->inv_valid = c->keep_inv && c->n_inv_tasks > 0;
+    const double* di = launch_inv_diag(c, st);
+    if (!P.fused) launch_forward(c, st, hb, di, nullptr, nullptr);
+    launch_backward(c, st, di, nullptr, nullptr, nullptr, nullptr);
+    // the inverse after the backward (which, as a refactoring iteration of the gated loop, chains):
+    // the chord steps of dpg_chol_resolve then do the same arithmetic as the gated loop's
+    c->inv_valid = c->keep_inv && P.n_inv_tasks > 0;
     if (c->inv_valid) launch_inv(c, st, nullptr);
     return hipGetLastError() == hipSuccess ? DPG_OK : DPG_ERR_HIP;
 }
@@ -3146,7 +2557,7 @@ extern "C" void dpg_chol_track_factor(void* h, int on) {
     c->track = on != 0;
     c->fac_valid = false;
     c->sym_is_fac = false;
-    c->cur_G.clear();   // the current analysis was planned untracked: its team sizes are unknown
+    c->plan.cur_G.clear();   // the current analysis was planned untracked: its team sizes are unknown
 }
 extern "C" void dpg_chol_forget_factor(void* h) {
     if (!h) return;
@@ -3180,10 +2591,11 @@ extern "C" int dpg_chol_solve_partial(void* h, const double* hb, const int32_t* 
     CholDev* c = reinterpret_cast<CholDev*>(h);
     const dpg_chol_sym& S = c->sym;
     const dpg_chol_sym& O = c->fac_sym;
+    const CholPlan& P = c->plan;
     const bool usable = c->track && c->fac_valid && !c->sym_is_fac && c->fac_ptr == c->fronts &&
-                        c->fac_ysol == c->ysol && c->fac_acc == c->acc && c->fused &&
-                        !(c->use_dinv && c->n_dblocks > 0) && c->fac_db == c->fused_db && O.ns > 0 && O.n <= S.n &&
-                        (int64_t)c->fac_G.size() == (int64_t)O.ns && (int64_t)c->cur_G.size() == (int64_t)S.ns &&
+                        c->fac_ysol == c->ysol && c->fac_acc == c->acc && P.fused &&
+                        !(P.use_dinv && P.n_dblocks > 0) && c->fac_db == P.fused_db && O.ns > 0 && O.n <= S.n &&
+                        (int64_t)c->fac_G.size() == (int64_t)O.ns && (int64_t)P.cur_G.size() == (int64_t)S.ns &&
                         std::equal(O.perm.begin(), O.perm.end(), S.perm.begin());
     if (!usable) return dpg_chol_solve(h, hb, stream);
     const double t_pick = wall_ms();
@@ -3205,7 +2617,7 @@ extern "C" int dpg_chol_solve_partial(void* h, const double* hb, const int32_t* 
             int32_t os = -1;
             if (same) {
                 os = O.sn_of[(size_t)c0];
-                same = O.sn_c0[(size_t)os] == c0 && O.sn_c0[(size_t)os + 1] == c1 && c->fac_G[(size_t)os] == c->cur_G[(size_t)sn];
+                same = O.sn_c0[(size_t)os] == c0 && O.sn_c0[(size_t)os + 1] == c1 && c->fac_G[(size_t)os] == P.cur_G[(size_t)sn];
             }
             if (same) {
                 const int64_t r0 = S.sn_rows_ptr[(size_t)sn], r1 = S.sn_rows_ptr[(size_t)sn + 1];
@@ -3230,7 +2642,7 @@ extern "C" int dpg_chol_solve_partial(void* h, const double* hb, const int32_t* 
     }
     if (kept == 0) return dpg_chol_solve(h, hb, stream);
     // runs of kept fronts the layout moved: gather {old, scratch}, scatter {scratch, new}; the
-    // pending updates of front s sit at 3 sn_rows_ptr[s] (chol_plan's acc_off)
+    // pending updates of front s sit at 3 sn_rows_ptr[s] (the plan's acc_off)
     std::vector<int64_t>& runs = c->h_runs;
     runs.clear();
     int64_t moved = 0, max_run = 0;
@@ -3299,16 +2711,11 @@ extern "C" int dpg_chol_solve_partial(void* h, const double* hb, const int32_t* 
         hipLaunchKernelGGL(chol_copy_runs, dim3(gx, (unsigned)nruns), dim3(256), 0, st, c->scratch, c->scratch, c->fronts,
                            c->acc, sca_dev);
     }
-    const double* g = hb + 9 * c->nnzb_upper;
     if (hipMemsetAsync(c->status, 0, sizeof(int32_t), st) != hipSuccess ||
-        hipMemsetAsync(c->sync, 0, c->sync_bytes, st) != hipSuccess)
+        hipMemsetAsync(c->sync, 0, P.sync_bytes, st) != hipSuccess)
         return DPG_ERR_HIP;
-    hipLaunchKernelGGL(chol_factor_dag, dim3((unsigned)c->n_tickets), dim3(kFT), c->lds_fused, st, c->order_fac,
-                       c->sync, c->status, c->sns, c->omap, c->relmap, c->child_list, c->ftasks, c->fchild, hb, g,
-                       c->perm, c->fronts, c->ysol, c->acc, ns, c->fused_db ? 1 : 0, nullptr, keep_dev);
-    hipLaunchKernelGGL(chol_backward_dag, dim3(ns), dim3(kT), c->lds_solve_max, st, c->order_bwd,
-                       c->sync + 1 + 2 * ns, c->status, c->sns, c->rows, c->segs, c->fronts, c->ysol, c->xsol,
-                       c->solve_stage, c->solve_maxseg, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    launch_factor(c, st, hb, nullptr, keep_dev);
+    launch_backward(c, st, nullptr, nullptr, nullptr, nullptr, nullptr);
     note_factored(c, ns - kept, kept, moved, (int64_t)((wall_ms() - t_pick) * 1e6));
     c->inv_valid = false;
     return hipGetLastError() == hipSuccess ? DPG_OK : DPG_ERR_HIP;
@@ -3318,17 +2725,11 @@ extern "C" int dpg_chol_solve_partial(void* h, const double* hb, const int32_t* 
 extern "C" int dpg_chol_resolve(void* h, const double* hb, void* stream) {
     CholDev* c = reinterpret_cast<CholDev*>(h);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const dpg_chol_sym& S = c->sym;
-    const double* g = hb + 9 * c->nnzb_upper;
-    if (hipMemsetAsync(c->sync, 0, c->sync_bytes, st) != hipSuccess) return DPG_ERR_HIP;
-    const double* di = c->use_dinv ? c->dinv : nullptr;   // inverted by the factorization's dpg_chol_solve
+    if (hipMemsetAsync(c->sync, 0, c->plan.sync_bytes, st) != hipSuccess) return DPG_ERR_HIP;
+    const double* di = c->plan.use_dinv ? c->dinv : nullptr;   // inverted by the factorization's dpg_chol_solve
     const double* li = c->inv_valid ? c->linv : nullptr;
-    hipLaunchKernelGGL(chol_forward_dag, dim3(S.ns), dim3(kT), c->lds_solve_max, st, c->order_fwd, c->sync, c->status,
-                       c->sns, c->child_list, c->relmap, c->fronts, g, c->perm, c->ysol, c->acc, c->solve_stage, di, nullptr,
-                       li);
-    hipLaunchKernelGGL(chol_backward_dag, dim3(S.ns), dim3(kT), c->lds_solve_max, st, c->order_bwd,
-                       c->sync + 1 + 2 * S.ns, c->status, c->sns, c->rows, c->segs, c->fronts, c->ysol, c->xsol, c->solve_stage,
-                       c->solve_maxseg, di, nullptr, nullptr, nullptr, nullptr, li);
+    launch_forward(c, st, hb, di, nullptr, li);
+    launch_backward(c, st, di, nullptr, nullptr, nullptr, li);
     return hipGetLastError() == hipSuccess ? DPG_OK : DPG_ERR_HIP;
 }
 
@@ -3337,13 +2738,13 @@ extern "C" int dpg_chol_resolve(void* h, const double* hb, void* stream) {
 // backward solve.  Only the fused plan without inverted diagonal blocks (dpg_chol_gated_ok).
 extern "C" int dpg_chol_gated_ok(void* h) {
     const CholDev* c = reinterpret_cast<const CholDev*>(h);
-    return c && c->fused && !(c->use_dinv && c->n_dblocks > 0) ? 1 : 0;
+    return c && c->plan.fused && !(c->plan.use_dinv && c->plan.n_dblocks > 0) ? 1 : 0;
 }
 
 extern "C" void dpg_chol_sync_dev(void* h, int32_t** sync, int64_t* n_words) {
     CholDev* c = reinterpret_cast<CholDev*>(h);
     *sync = c->sync;
-    *n_words = (int64_t)(c->sync_bytes / sizeof(int32_t));
+    *n_words = (int64_t)(c->plan.sync_bytes / sizeof(int32_t));
 }
 
 // prezeroed: the caller's previous launch cleared the status word and the sync counters
@@ -3354,12 +2755,10 @@ extern "C" int dpg_chol_solve_gated(void* h, const double* hb, const int32_t* ga
     c->fac_valid = false;   // (a Gauss-Newton loop's refactorizations are not tracked)
     c->has_factor = true;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const dpg_chol_sym& S = c->sym;
-    const double* g = hb + 9 * c->nnzb_upper;
     if (!prezeroed && (hipMemsetAsync(c->status, 0, sizeof(int32_t), st) != hipSuccess ||
-                       hipMemsetAsync(c->sync, 0, c->sync_bytes, st) != hipSuccess))
+                       hipMemsetAsync(c->sync, 0, c->plan.sync_bytes, st) != hipSuccess))
         return DPG_ERR_HIP;
-    const bool inv = c->n_inv_tasks > 0;
+    const bool inv = c->plan.n_inv_tasks > 0;
     if (inv) {   // this iteration's solves come after the previous iteration's inverse
         if (!c->aux) {
             if (hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking) != hipSuccess ||
@@ -3371,9 +2770,7 @@ extern "C" int dpg_chol_solve_gated(void* h, const double* hb, const int32_t* ga
         }
         if (hipStreamWaitEvent(st, c->ev_inv[c->inv_par ^ 1], 0) != hipSuccess) return DPG_ERR_HIP;
     }
-    hipLaunchKernelGGL(chol_factor_dag, dim3((unsigned)c->n_tickets), dim3(kFT), c->lds_fused, st, c->order_fac,
-                       c->sync, c->status, c->sns, c->omap, c->relmap, c->child_list, c->ftasks, c->fchild, hb, g,
-                       c->perm, c->fronts, c->ysol, c->acc, S.ns, c->fused_db ? 1 : 0, gate, nullptr);
+    launch_factor(c, st, hb, gate, nullptr);
     if (inv) {   // L11^-1 of a refactoring iteration beside its backward solve (which does not use it)
         if (hipEventRecord(c->ev_fac, st) != hipSuccess || hipStreamWaitEvent(c->aux, c->ev_fac, 0) != hipSuccess)
             return DPG_ERR_HIP;
@@ -3381,12 +2778,8 @@ extern "C" int dpg_chol_solve_gated(void* h, const double* hb, const int32_t* ga
         if (hipEventRecord(c->ev_inv[c->inv_par], c->aux) != hipSuccess) return DPG_ERR_HIP;
         c->inv_par ^= 1;
     }
-    hipLaunchKernelGGL(chol_forward_dag, dim3(S.ns), dim3(kT), c->lds_solve_max, st, c->order_fwd, c->sync, c->status,
-                       c->sns, c->child_list, c->relmap, c->fronts, g, c->perm, c->ysol, c->acc, c->solve_stage,
-                       nullptr, gate, c->linv);
-    hipLaunchKernelGGL(chol_backward_dag, dim3(S.ns), dim3(kT), c->lds_solve_max, st, c->order_bwd,
-                       c->sync + 1 + 2 * S.ns, c->status, c->sns, c->rows, c->segs, c->fronts, c->ysol, c->xsol,
-                       c->solve_stage, c->solve_maxseg, nullptr, gate, c->perm, X, max_out, c->linv);
+    launch_forward(c, st, hb, nullptr, gate, c->linv);
+    launch_backward(c, st, nullptr, gate, X, max_out, c->linv);
     return hipGetLastError() == hipSuccess ? DPG_OK : DPG_ERR_HIP;
 }
 

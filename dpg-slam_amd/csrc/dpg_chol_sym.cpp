@@ -1,7 +1,8 @@
 // dpg_chol_sym.cpp -- symbolic analysis of the block-sparse pose-graph system for the GPU
 // supernodal multifrontal Cholesky (the CHOLESKY linear solver GTSAM runs inside
 // ISAM2 / GaussNewtonOptimizer).  Host code, run once per sparsity pattern
-// (dpg_gn_setup); the numeric factorization and solves are in dpg_chol.hip.
+// (dpg_gn_setup); the solver's host planner is dpg_chol_plan.cpp, the numeric factorization and
+// solves are in dpg_chol.hip.
 //
 //   1. fill-reducing order on the 3x3-block graph: nested dissection (BFS level separators) down
 //      to parts of <= 16 nodes, ordered by minimum degree (bitset elimination graphs, ties ->
@@ -27,6 +28,7 @@
 #include <vector>
 
 #include "dpg_chol.h"
+#include "dpg_chol_plan.h"
 
 namespace {
 
@@ -706,10 +708,9 @@ int dpg_chol_order(int64_t n, const int32_t* pair_lo, const int32_t* pair_hi, in
     return 0;
 }
 
-// The fused factorization's critical path estimate (us) of a symbolic analysis: the same per-front
-// model chol_plan orders its tickets by (dpg_chol.hip: a front of <= 96 rows and <= 8 children is
-// factored in LDS, 4 + 0.06 m3 + 0.9 k3; a larger one by a team, 10 + 20 per 24-column panel),
-// summed along the longest leaf-to-root path
+// The fused factorization's critical path estimate (us) of a symbolic analysis: the per-front model
+// the planner orders its tickets by (front_est_us, dpg_chol_plan.h), summed along the longest
+// leaf-to-root path
 double dpg_chol_critical_path_us(const dpg_chol_sym& S) {
     std::vector<double> cp((size_t)S.ns, 0.0);
     double crit = 0.0;
@@ -717,10 +718,8 @@ double dpg_chol_critical_path_us(const dpg_chol_sym& S) {
         const int32_t k = S.sn_c0[(size_t)s + 1] - S.sn_c0[(size_t)s];
         const int32_t r = (int32_t)(S.sn_rows_ptr[(size_t)s + 1] - S.sn_rows_ptr[(size_t)s]);
         const int32_t nch = (int32_t)(S.child_ptr[(size_t)s + 1] - S.child_ptr[(size_t)s]);
-        const int32_t m3 = 3 * (k + r);
-        const double est = (m3 <= 96 && nch <= 8) ? 4.0 + 0.06 * m3 + 0.9 * (3 * k) : 10.0 + 20.0 * ((3 * k + 23) / 24);
         const int32_t p = S.sn_parent[(size_t)s];
-        cp[(size_t)s] = est + (p >= 0 ? cp[(size_t)p] : 0.0);
+        cp[(size_t)s] = dpg_chol::front_est_us(3 * (k + r), 3 * k, nch) + (p >= 0 ? cp[(size_t)p] : 0.0);
         crit = std::max(crit, cp[(size_t)s]);
     }
     return crit;

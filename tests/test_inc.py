@@ -55,18 +55,19 @@ def test_threaded_nested_dissection_gives_the_serial_order(tmp_path, n, seed):
 
 
 def test_solver_plan_matches_straightforward_construction(tmp_path):
-    """The GPU solver's host plan (dpg_chol.hip chol_plan: H-block -> front map by column buckets,
+    """The GPU solver's host plan (dpg_chol_plan.cpp: H-block -> front map by column buckets,
     child column ranges by binary search, critical-path front order) equals the straightforward
     construction (per-block binary search + per-front sort, linear scans, stable sort) after every
     update of a growing graph: tools/incsym_bench.cpp built with DPG_PLAN_VERIFY aborts on the first
     difference -- including the H-block buckets the incremental prepare builds ahead from the
-    incremental state's order (dpg_chol_plan_blocks, every 50th update) and that order against the
-    analysis's.  Host code only (hipcc compiles it; no device call runs)."""
+    incremental state's order (dpg_chol_plan_prebucket, every 50th update), that order against the
+    analysis's, and the largest ticket priority against the critical-path estimate the analysis
+    picked its order by.  Plain C++: the planner and the symbolic analysis build without HIP."""
     exe = str(tmp_path / "incsym_bench_v")
     csrc = os.path.join(ROOT, "dpg-slam_amd", "csrc")
-    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O2", "-std=c++17", "-ffp-contract=off",
-                    "-DDPG_PLAN_VERIFY", "-o", exe, os.path.join(ROOT, "tools", "incsym_bench.cpp"),
-                    os.path.join(csrc, "dpg_chol.hip"), os.path.join(csrc, "dpg_chol_sym.cpp")], check=True)
+    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-pthread", "-DDPG_PLAN_VERIFY", "-o", exe,
+                    os.path.join(ROOT, "tools", "incsym_bench.cpp"), os.path.join(csrc, "dpg_chol_plan.cpp"),
+                    os.path.join(csrc, "dpg_chol_sym.cpp")], check=True)
     rng = np.random.default_rng(5)
     V, buf = 700, [700]
     for v in range(V):

@@ -1,7 +1,8 @@
 // incsym_bench.cpp -- CPU timing of the incremental path's host symbolic work per update
 // (dpg_inc_update, dpg-slam_amd/csrc/dpg_inc.hip: ordering kept/extended or refreshed every 64
 // nodes, the derived structures, the GPU solver's host plan) on a recorded arrival sequence
-// (tools/dump_inc_edges.py).  No device calls.
+// (tools/dump_inc_edges.py).  Host code only: built with the C++ compiler against
+// dpg_chol_sym.cpp and dpg_chol_plan.cpp.
 // usage: incsym_bench EDGES.bin [TAIL]   prints mean ms per part over the last TAIL updates
 #include <stdio.h>
 #include <stdlib.h>
@@ -11,6 +12,7 @@
 #include <vector>
 
 #include "../dpg-slam_amd/csrc/dpg_chol.h"
+#include "../dpg-slam_amd/csrc/dpg_chol_plan.h"
 
 #ifdef DPG_PLAN_TIMING
 extern double dpg_plan_t_export[8];
@@ -106,19 +108,18 @@ int main(int argc, char** argv) {
         }
 #ifdef DPG_PLAN_VERIFY
         // the incremental prepare builds the plan's H-block buckets from I's order beside the
-        // derivation (dpg_chol_plan_blocks): that order must be the one the analysis carries, and
-        // the plan checks the prebuilt buckets against its own (every 50th update: host only)
+        // derivation (dpg_chol_plan_blocks -> dpg_chol_plan_prebucket): that order must be the one
+        // the analysis carries, and the plan checks the prebuilt buckets against its own (every
+        // 50th update)
         if (I.perm != S.perm || I.pos != S.pos) { fprintf(stderr, "update %d: I and S orders differ\n", v); abort(); }
         if (v % 50 == 49) {
-            static void* hv = nullptr;
-            dpg_chol_sym S3 = S;
-            if (dpg_chol_plan_blocks(&hv, V1, I.pos.data(), I.perm.data(), plo.data(), phi.data(), (int64_t)plo.size()) ||
-                dpg_chol_create_sym_plan(&hv, V1, plo.data(), phi.data(), (int64_t)plo.size(), &S3, &o))
-                return 6;
+            static dpg_chol::CholPlan pv;
+            dpg_chol_plan_prebucket(pv, V1, I.pos.data(), I.perm.data(), plo.data(), phi.data(), (int64_t)plo.size());
+            if (dpg_chol_plan_build(pv, S, o, false, V1, plo.data(), phi.data(), (int64_t)plo.size())) return 6;
         }
 #endif
         double plan = 0;
-        if (dpg_chol_plan_host(V1, plo.data(), phi.data(), (int64_t)plo.size(), &S, &plan)) return 5;
+        if (dpg_chol_plan_host(V1, plo.data(), phi.data(), (int64_t)plo.size(), &S, &o, &plan)) return 5;
         if (v >= V - tail) {
             acc[0] += t1 - t0;
             acc[1] += t2 - t1;
@@ -126,20 +127,7 @@ int main(int argc, char** argv) {
             flops += S.flops;
             maxf = std::max<double>(maxf, S.max_front);
             levels += S.n_levels;
-            // the critical-path estimate the fused factorization schedules by (dpg_chol.hip chol_plan)
-            std::vector<double> cpe((size_t)S.ns, 0.0);
-            double crit = 0.0;
-            for (int32_t s = S.ns - 1; s >= 0; --s) {
-                const int32_t k = S.sn_c0[(size_t)s + 1] - S.sn_c0[(size_t)s];
-                const int32_t r = (int32_t)(S.sn_rows_ptr[(size_t)s + 1] - S.sn_rows_ptr[(size_t)s]);
-                const int32_t nch = (int32_t)(S.child_ptr[(size_t)s + 1] - S.child_ptr[(size_t)s]);
-                const int32_t m3 = 3 * (k + r);
-                const double est = (m3 <= 96 && nch <= 8) ? 4.0 + 0.05 * m3 : 10.0 + 20.0 * ((3 * k + 23) / 24);
-                const int32_t pa = S.sn_parent[(size_t)s];
-                cpe[(size_t)s] = est + (pa >= 0 ? cpe[(size_t)pa] : 0.0);
-                crit = std::max(crit, cpe[(size_t)s]);
-            }
-            crit_sum += crit;
+            crit_sum += dpg_chol_critical_path_us(S);   // what the fused factorization schedules by
             ++cnt;
         }
     }

@@ -1,9 +1,8 @@
 // order_eval.cpp -- compare fill-reducing orders for the GPU Cholesky on a pose graph (host only):
 // minimum degree vs nested dissection (several leaf sizes).  For each: fill (blocks), factor Mflop,
 // supernodes, elimination-tree levels, largest front and the critical-path estimate the fused DAG
-// factorization schedules by (dpg_chol.hip chol_plan: 4 + 0.06 m3 + 0.9 k3 us for a small front, 10 + 20 us
-// per 24-column panel for a large one, summed along the longest leaf-to-root path), plus the
-// ordering time.
+// factorization schedules by (front_est_us, dpg_chol_plan.h, summed along the longest leaf-to-root
+// path), plus the ordering time.
 // usage: order_eval PAIRS.bin        (int32 n, int32 P, then P x (lo, hi))
 #include <stdio.h>
 #include <stdlib.h>
@@ -13,6 +12,7 @@
 #include <vector>
 
 #include "../dpg-slam_amd/csrc/dpg_chol.h"
+#include "../dpg-slam_amd/csrc/dpg_chol_plan.h"
 
 static double now_ms() {
     struct timespec ts;
@@ -26,18 +26,12 @@ static void report(const char* name, double ms, const dpg_chol_sym& S) {
         const int64_t k = S.sn_c0[(size_t)s + 1] - S.sn_c0[(size_t)s], r = S.sn_rows_ptr[(size_t)s + 1] - S.sn_rows_ptr[(size_t)s];
         nnz += k * (k - 1) / 2 + k * r;
     }
-    std::vector<double> cp((size_t)S.ns, 0.0);
-    double crit = 0.0, work = 0.0;
-    for (int32_t s = S.ns - 1; s >= 0; --s) {   // parents after children: walk down from the roots
+    const double crit = dpg_chol_critical_path_us(S);
+    double work = 0.0;
+    for (int32_t s = 0; s < S.ns; ++s) {
         const int32_t k = S.sn_c0[(size_t)s + 1] - S.sn_c0[(size_t)s];
         const int32_t r = (int32_t)(S.sn_rows_ptr[(size_t)s + 1] - S.sn_rows_ptr[(size_t)s]);
-        const int32_t nch = (int32_t)(S.child_ptr[(size_t)s + 1] - S.child_ptr[(size_t)s]);
-        const int32_t m3 = 3 * (k + r);
-        const double est = (m3 <= 96 && nch <= 8) ? 4.0 + 0.06 * m3 + 0.9 * (3 * k) : 10.0 + 20.0 * ((3 * k + 23) / 24);
-        const int32_t p = S.sn_parent[(size_t)s];
-        cp[(size_t)s] = est + (p >= 0 ? cp[(size_t)p] : 0.0);
-        crit = std::max(crit, cp[(size_t)s]);
-        work += est;
+        work += dpg_chol::front_est_us(3 * (k + r), 3 * k, (int32_t)(S.child_ptr[(size_t)s + 1] - S.child_ptr[(size_t)s]));
     }
     printf("%-10s order %8.2f ms | fill %8lld blocks, %8.1f Mflop, %5d supernodes, %4d levels, max front %4d | "
            "critical path ~%7.0f us, work ~%8.0f us\n",

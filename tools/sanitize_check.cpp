@@ -1,10 +1,12 @@
 // sanitize_check.cpp -- the host C / C++ code under AddressSanitizer + UndefinedBehaviorSanitizer
 // (`make -C oracle sanitize`, run by tests/test_sanitize.py in the CPU suite): the oracle
 // (dpg_oracle.c, dpg_change_oracle.cpp), the host half of the C ABI (csrc/dpg_host.c), the
-// synthetic workload generator (csrc/dpg_synth.c) and the symbolic Cholesky analysis, full and
-// incremental (csrc/dpg_chol_sym.cpp), driven through a small end-to-end workload: scans ->
-// clouds -> batched ICP + covariance -> factors -> Gauss-Newton -> symbolic analysis -> DPG change
-// detection over two passes.  Any sanitizer report aborts (-fno-sanitize-recover).
+// synthetic workload generator (csrc/dpg_synth.c), the symbolic Cholesky analysis, full and
+// incremental (csrc/dpg_chol_sym.cpp), and the GPU solver's host planner (csrc/dpg_chol_plan.cpp:
+// its tables are followed by the kernels without bounds checks), driven through a small
+// end-to-end workload: scans -> clouds -> batched ICP + covariance -> factors -> Gauss-Newton ->
+// symbolic analysis -> solver plans -> DPG change detection over two passes.  Any sanitizer report
+// aborts (-fno-sanitize-recover).
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
@@ -12,6 +14,7 @@
 #include <vector>
 
 #include "../dpg-slam_amd/csrc/dpg_chol.h"
+#include "../dpg-slam_amd/csrc/dpg_chol_plan.h"
 #include "../oracle/dpg_oracle.h"
 
 struct oracle_dpg;
@@ -30,6 +33,72 @@ int64_t oracle_active_dynamic_points(oracle_dpg* o, int64_t V, const float* est,
     do {                                                                   \
         if (!(c)) { fprintf(stderr, "FAIL %s:%d %s\n", __FILE__, __LINE__, #c); return 1; } \
     } while (0)
+
+// The solver plan of one graph under each option set that selects another branch of the planner
+// (the fused DAG path, the level path, L11^-1 tasks, inverted diagonal blocks), tracked and not,
+// and once more from buckets prebuilt ahead of the plan.  want_team: the graph must have a front
+// factored by a team, and its level plan a step with trailing-update tiles.
+static int plan_graph(int64_t n, const std::vector<int32_t>& lo, const std::vector<int32_t>& hi, bool want_team) {
+    using dpg_chol::CholPlan;
+    const int64_t np = (int64_t)lo.size();
+    dpg_chol_opts base{64, 0.3};
+    dpg_chol_sym S;
+    REQUIRE(dpg_chol_symbolic(n, lo.data(), hi.data(), np, &base, &S) == 0);
+    dpg_chol_opts sets[4] = {base, base, base, base};
+    sets[1].fused = 0;
+    sets[2].solve_inv_cols = 48;
+    sets[3].solve_dinv = 1;
+    CholPlan P;   // one plan object reused, as the solver reuses its own between builds
+    for (int k = 0; k < 4; ++k)
+        for (int track = 0; track < 2; ++track) {
+            REQUIRE(dpg_chol_plan_build(P, S, sets[k], track != 0, n, lo.data(), hi.data(), np) == DPG_OK);
+            REQUIRE(P.fused == (k != 1) && (int64_t)P.sns.size() == S.ns && (int64_t)P.bwd.size() == S.ns);
+            REQUIRE((P.n_inv_tasks > 0) == (k == 2) && P.use_dinv == (k == 3) && P.n_dblocks >= S.ns);
+            REQUIRE(!track || (int64_t)P.cur_G.size() == S.ns);
+            bool team = false, upd = false;
+            for (const dpg_chol::SnDev& d : P.sns) team = team || d.G > 1;
+            for (const CholPlan::Level& L : P.levels)
+                for (const CholPlan::Step& st : L.steps) upd = upd || st.upd_cnt > 0;
+            if (want_team) REQUIRE(team && !P.ftasks.empty());
+            if (want_team && k == 1) REQUIRE(upd);
+            REQUIRE((k == 1) == !P.levels.empty());
+        }
+    const std::vector<dpg_chol::OEnt> omap = P.omap;
+    dpg_chol_plan_prebucket(P, n, S.pos.data(), S.perm.data(), lo.data(), hi.data(), np);
+    REQUIRE(dpg_chol_plan_build(P, S, base, false, n, lo.data(), hi.data(), np) == DPG_OK);
+    REQUIRE(P.omap.size() == omap.size() && memcmp(P.omap.data(), omap.data(), omap.size() * sizeof(omap[0])) == 0);
+    double ms = 0;
+    REQUIRE(dpg_chol_plan_host(n, lo.data(), hi.data(), np, &S, nullptr, &ms) == DPG_OK);
+    return 0;
+}
+
+static int plan_checks() {
+    std::vector<int32_t> lo, hi;
+    const int M = 30;   // M x M 4-neighbour mesh: separator fronts past the in-LDS limit (teams)
+    for (int r = 0; r < M; ++r)
+        for (int c = 0; c < M; ++c) {
+            if (c + 1 < M) { lo.push_back(r * M + c); hi.push_back(r * M + c + 1); }
+            if (r + 1 < M) { lo.push_back(r * M + c); hi.push_back((r + 1) * M + c); }
+        }
+    REQUIRE(plan_graph(M * M, lo, hi, true) == 0);
+    // a 700-node chain with up to three random loop closures per node (tests/test_inc.py's graph)
+    lo.clear();
+    hi.clear();
+    uint32_t x = 5;
+    auto rnd = [&x](uint32_t m) { x = x * 1664525u + 1013904223u; return (int32_t)((x >> 8) % m); };
+    for (int v = 1; v < 700; ++v) {
+        int32_t e[4] = {v - 1, -1, -1, -1};
+        int ne = 1;
+        for (int k = v > 20 ? rnd(4) : 0; k > 0; --k) {
+            const int32_t u = rnd((uint32_t)(v - 10));
+            if (std::find(e, e + ne, u) == e + ne) e[ne++] = u;
+        }
+        for (int k = 0; k < ne; ++k) { lo.push_back(e[k]); hi.push_back(v); }
+    }
+    REQUIRE(plan_graph(700, lo, hi, false) == 0);
+    printf("solver plans ok: %d x %d mesh, 700-node loop graph\n", M, M);
+    return 0;
+}
 
 int main() {
     const int V = 24, NB = 720;
@@ -118,6 +187,8 @@ int main() {
         dpg_chol_sym S2;
         REQUIRE(dpg_incsym_derive(&I, &o, &S2) == 0);
     }
+    // the GPU solver's host plans of larger graphs
+    REQUIRE(plan_checks() == 0);
     // DPG change detection: pass 0 = the first half, pass 1 = the second half as a later pass
     dpg_change_params cp;
     memset(&cp, 0, sizeof(cp));
