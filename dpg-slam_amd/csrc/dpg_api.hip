@@ -2181,6 +2181,69 @@ int dpg_gn_marginal_pairs(dpg_ctx* c, const int32_t* pairs, int64_t n, double* c
     return gn_marginals_blocks(c, "dpg_gn_marginal_pairs", nullptr, 0, pairs, n, cov_out, nullptr);
 }
 
+// ---- joint marginals and relative-pose covariances of any node pair (Marginals::jointMarginalCovariance) ----
+// The same linearization and factorization as above, then the blocks from root paths of the factor
+// (dpg_chol_joint): no pattern restriction.  The relative-pose Jacobian is 3x3 arithmetic per pair
+// on the host (dpg_relative_covariance), at the poses the factor was linearized at.
+static int gn_joint_blocks(dpg_ctx* c, const char* fn, int by_nodes, const int32_t* idx, int64_t n, double* out, float* ms) {
+    int rc = gn_marginals_state(c, fn);
+    if (rc) return rc;
+    if (n < 0 || (n > 0 && (!idx || !out))) return fail(DPG_ERR_ARG, "%s: bad arguments", fn);
+    for (int64_t q = 0, e = by_nodes ? n : 2 * n; q < e; ++q)
+        if (idx[q] < 0 || idx[q] >= c->gn.n_nodes) return fail(DPG_ERR_ARG, "%s: node %d is out of range", fn, idx[q]);
+    if (n == 0) return DPG_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    dpg_gn_dev* g = &c->gn;
+    if ((rc = dpg_gn_dev_assemble(g, g->hb_own, c->stream))) return fail(rc, "%s: assembly launch failed", fn);
+    if ((rc = dpg_chol_solve(g->chol, g->hb_own, c->stream))) return fail(rc, "%s: factorization launch failed", fn);
+    rc = dpg_chol_joint(g->chol, by_nodes, idx, n, out, c->stream, ms);
+    if (rc == DPG_ERR_NUMERIC) return fail(rc, "%s: H is not positive definite", fn);
+    if (rc) return fail(rc, "%s: the path solve failed", fn);
+    return DPG_OK;
+}
+
+int dpg_gn_cross_covariances(dpg_ctx* c, const int32_t* pairs, int64_t n, double* cov_out) {
+    return gn_joint_blocks(c, "dpg_gn_cross_covariances", 0, pairs, n, cov_out, nullptr);
+}
+
+int dpg_gn_joint_marginal(dpg_ctx* c, const int32_t* nodes, int64_t n, double* cov_out) {
+    return gn_joint_blocks(c, "dpg_gn_joint_marginal", 1, nodes, n, cov_out, nullptr);
+}
+
+int dpg_gn_relative_covariances(dpg_ctx* c, const int32_t* pairs, int64_t n, double* cov_out) {
+    const char* fn = "dpg_gn_relative_covariances";
+    int rc = gn_marginals_state(c, fn);
+    if (rc) return rc;
+    if (n < 0 || (n > 0 && (!pairs || !cov_out))) return fail(DPG_ERR_ARG, "%s: bad arguments", fn);
+    if (n == 0) return DPG_OK;
+    for (int64_t q = 0; q < 2 * n; ++q)
+        if (pairs[q] < 0 || pairs[q] >= c->gn.n_nodes) return fail(DPG_ERR_ARG, "%s: node %d is out of range", fn, pairs[q]);
+    std::vector<int32_t> tri((size_t)(6 * n));
+    dpg_relative_triples(pairs, n, tri.data());
+    std::vector<double> blocks((size_t)(27 * n)), X((size_t)(3 * c->gn.n_nodes));
+    if ((rc = gn_joint_blocks(c, fn, 0, tri.data(), 3 * n, blocks.data(), nullptr))) return rc;
+    if ((rc = dpg_gn_get_poses(c, X.data()))) return rc;
+    dpg_relative_from_blocks(pairs, n, X.data(), blocks.data(), cov_out);
+    return DPG_OK;
+}
+
+/* Diagnostic (tools/joint_probe.py): one dpg_gn_cross_covariances with its two kernels timed by HIP
+ * events.  out = {path solve ms, dot ms, the longest root path in fronts, in pivot scalars}. */
+int dpg_gn_joint_profile(dpg_ctx* c, const int32_t* pairs, int64_t n, double* out, int64_t cap) {
+    if (!out || cap < 4 || n <= 0) return fail(DPG_ERR_ARG, "dpg_gn_joint_profile: bad arguments");
+    std::vector<double> cov((size_t)(9 * n));
+    float ms[2] = {0.f, 0.f};
+    const int rc = gn_joint_blocks(c, "dpg_gn_joint_profile", 0, pairs, n, cov.data(), ms);
+    if (rc) return rc;
+    int64_t st[2];
+    dpg_chol_path_stats(c->gn.chol, st);
+    out[0] = ms[0];
+    out[1] = ms[1];
+    out[2] = (double)st[0];
+    out[3] = (double)st[1];
+    return DPG_OK;
+}
+
 int dpg_marginal_covariances(dpg_ctx* c, const double* poses, int64_t V, const dpg_factor* F, int64_t nf,
                              const int32_t* nodes, int64_t n, double* cov_out) {
     if (!c || !F || !poses || !cov_out || V <= 0 || nf < 0 || n < 0 || (!nodes && n != V))

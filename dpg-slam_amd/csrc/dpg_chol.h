@@ -1,7 +1,8 @@
 // dpg_chol.h -- GPU supernodal multifrontal Cholesky for the 3x3-block pose-graph system
 // (private, C++).  Symbolic analysis in dpg_chol_sym.cpp; host planner (analysis -> index tables and
 // launch parameters, plain C++) in dpg_chol_plan.cpp; kernels and driver (upload, factorization,
-// solves, selected inverse) in dpg_chol.hip.  dpg_chol_plan.h holds what planner and kernels share.
+// solves, selected inverse, joint marginals) in dpg_chol.hip.  dpg_chol_plan.h holds what planner and
+// kernels share.
 #ifndef DPG_CHOL_H
 #define DPG_CHOL_H
 

@@ -1,7 +1,8 @@
 // dpg_chol.hip -- supernodal multifrontal Cholesky of the pose-graph normal equations on gfx950.
 //
-// This file: the kernels (factorization, solves, selected inverse) and the host driver (CholDev,
-// the upload, one launch helper per kernel, the solve / selected-inverse / marginals entry points).
+// This file: the kernels (factorization, solves, selected inverse, joint marginals) and the host
+// driver (CholDev, the upload, one launch helper per kernel, the solve / selected-inverse /
+// marginals / joint-marginals entry points).
 // The host planner that builds every index table the kernels follow is dpg_chol_plan.cpp (plain
 // C++); the records, constants and cost model both sides share are in dpg_chol_plan.h.
 //
@@ -2111,6 +2112,146 @@ __global__ __launch_bounds__(256) void chol_selinv_pick(const SelPick* __restric
     out[e] = sel[p.off + (int64_t)jj * p.ld + ii];
 }
 
+// ---- joint marginals: blocks of Sigma outside L's pattern (any node pair) ----
+// With P H P^T = L L^T, Sigma(i, j) = W_i^T W_j, W_q = L^-1 E_q (E_q: node q's three unit columns).
+// W_q is nonzero only on the pivot rows of the fronts between q's own and the root of its tree, so
+// it takes one forward substitution along one root path -- the multifrontal forward solve's
+// hand-over, restricted to that path -- and no backward solve.
+//
+// chol_path_forward: one workgroup per queried node (every gridDim.x-th query).  It carries a
+// (front rows x 3) right-hand side: the identity at q's three pivot scalars in its own front.  Per
+// front, kPB pivot columns at a time: the diagonal block goes to LDS, one thread per right-hand side
+// substitutes through it (rows in registers, four accumulators per row: a dependent fp64 chain),
+// then one thread per row below -- the rest of the pivot rows and the update rows -- subtracts the
+// block's columns times the new values.  The pivot rows w_C go to the query's slice of W, the update
+// rows through relmap into the parent's (zeroed) vector.  L is read from the fronts as
+// chol_selinv_level reads it (column-major, leading dimension 3 (k + r), L11 above L21; the fused
+// and the level factorization leave the same, and opts.solve_inv_cols puts L11^-1 in a buffer of
+// its own).  The two vectors ([3][ldv] each) are in LDS when they fit kPathLds, in this
+// workgroup's slice of `work` otherwise.  Every element is one thread's sum in a fixed order.
+__global__ __launch_bounds__(kT) void chol_path_forward(const PathQuery* __restrict__ queries, int64_t nq,
+                                                        const SnDev* __restrict__ sns, const int32_t* __restrict__ relmap,
+                                                        const double* __restrict__ fronts, double* __restrict__ W,
+                                                        double* work, int ldv, int in_lds) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    __shared__ double s_d[kPB * kPB];   // the diagonal block, column-major
+    __shared__ double s_rd[kPB];        // 1 / its diagonal
+    __shared__ double s_w[3 * kPB];     // the block's new values, per right-hand side
+    const int tid = threadIdx.x;
+    double* v0 = in_lds ? sm : work + (int64_t)blockIdx.x * 6 * ldv;
+    for (int64_t q = blockIdx.x; q < nq; q += gridDim.x) {
+        double* cur = v0;
+        double* nxt = v0 + 3 * ldv;
+        const PathQuery Q = queries[q];
+        SnDev S = sns[Q.sn];
+        int64_t wo = Q.w_off;
+        {
+            const int m3 = 3 * (S.k + S.r);
+            for (int e = tid; e < 3 * m3; e += kT) {
+                const int a = e / m3, i = e % m3;
+                cur[a * ldv + i] = i == Q.row + a ? 1.0 : 0.0;
+            }
+        }
+        for (;;) {
+            const int k3 = 3 * S.k, r3 = 3 * S.r, m3 = k3 + r3;
+            const double* F = fronts + S.front_off;
+            for (int j0 = 0; j0 < k3; j0 += kPB) {
+                const int nb = min(kPB, k3 - j0);
+                for (int e = tid; e < nb * nb; e += kT) {
+                    const int jj = e % nb, cc = e / nb;
+                    if (jj >= cc) s_d[cc * kPB + jj] = F[(int64_t)(j0 + cc) * m3 + j0 + jj];
+                }
+                if (tid < nb) s_rd[tid] = 1.0 / F[(int64_t)(j0 + tid) * m3 + j0 + tid];
+                __syncthreads();   // (also: the previous block's row updates are in cur)
+                if (tid < 3) {
+                    double* x = cur + tid * ldv + j0;
+                    double b[kPB], w[kPB];
+#pragma unroll
+                    for (int jj = 0; jj < kPB; ++jj) b[jj] = jj < nb ? x[jj] : 0.0;
+#pragma unroll
+                    for (int jj = 0; jj < kPB; ++jj) {
+                        if (jj < nb) {
+                            double a4[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                            for (int cc = 0; cc < jj; ++cc) a4[cc & 3] = fma(s_d[cc * kPB + jj], w[cc], a4[cc & 3]);
+                            w[jj] = (b[jj] - ((a4[0] + a4[1]) + (a4[2] + a4[3]))) * s_rd[jj];
+                            x[jj] = w[jj];
+                            s_w[tid * kPB + jj] = w[jj];
+                        }
+                    }
+                }
+                __syncthreads();
+                for (int i = j0 + nb + tid; i < m3; i += kT) {
+                    double a4[3][4] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
+                    const double* li = F + (int64_t)j0 * m3 + i;
+#pragma unroll 4
+                    for (int cc = 0; cc < nb; ++cc) {
+                        const double l = li[(int64_t)cc * m3];
+#pragma unroll
+                        for (int a = 0; a < 3; ++a) a4[a][cc & 3] = fma(l, s_w[a * kPB + cc], a4[a][cc & 3]);
+                    }
+#pragma unroll
+                    for (int a = 0; a < 3; ++a) cur[a * ldv + i] -= (a4[a][0] + a4[a][1]) + (a4[a][2] + a4[a][3]);
+                }
+                // (the next block's staging rewrites s_d and s_rd, which only the substitution read)
+            }
+            __syncthreads();
+            for (int e = tid; e < 3 * k3; e += kT) W[wo + e] = cur[(e % 3) * ldv + e / 3];
+            wo += 3 * k3;
+            if (S.parent < 0) break;
+            const SnDev Pn = sns[S.parent];
+            const int mp3 = 3 * (Pn.k + Pn.r);
+            for (int e = tid; e < 3 * mp3; e += kT) nxt[(e / mp3) * ldv + e % mp3] = 0.0;
+            __syncthreads();
+            const int32_t* rm = relmap + S.rows_off;
+            for (int e = tid; e < 3 * r3; e += kT) {
+                const int a = e / r3, t = e % r3;
+                nxt[a * ldv + 3 * rm[t / 3] + t % 3] = cur[a * ldv + k3 + t];
+            }
+            __syncthreads();
+            double* t = cur;
+            cur = nxt;
+            nxt = t;
+            S = Pn;
+        }
+        __syncthreads();   // (the next query starts in v0)
+    }
+}
+
+// chol_path_dot: one wave per requested block.  Lane l sums the scalars l, l + 64, ... of the two
+// suffixes' nine products in order, then a fixed xor tree over the 64 lanes; an empty suffix (two
+// trees of the forest) gives exactly 0.  The block and / or its transpose are stored (PathPair).
+__global__ __launch_bounds__(256) void chol_path_dot(const PathPair* __restrict__ pairs, int64_t n,
+                                                     const double* __restrict__ W, double* __restrict__ out, int64_t ld) {
+    const int lane = threadIdx.x & 63;
+    const int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (p >= n) return;   // (whole wave)
+    const PathPair P = pairs[p];
+    const double* A = W + P.a;
+    const double* B = W + P.b;
+    double s[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int t = lane; t < P.len; t += 64) {
+        const double a0 = A[3 * (int64_t)t], a1 = A[3 * (int64_t)t + 1], a2 = A[3 * (int64_t)t + 2];
+        const double b0 = B[3 * (int64_t)t], b1 = B[3 * (int64_t)t + 1], b2 = B[3 * (int64_t)t + 2];
+        s[0] = fma(a0, b0, s[0]); s[1] = fma(a0, b1, s[1]); s[2] = fma(a0, b2, s[2]);
+        s[3] = fma(a1, b0, s[3]); s[4] = fma(a1, b1, s[4]); s[5] = fma(a1, b2, s[5]);
+        s[6] = fma(a2, b0, s[6]); s[7] = fma(a2, b1, s[7]); s[8] = fma(a2, b2, s[8]);
+    }
+#pragma unroll
+    for (int e = 0; e < 9; ++e)
+        for (int off = 32; off >= 1; off >>= 1) s[e] += __shfl_xor(s[e], off, 64);
+    // (every lane holds the sums; lane e stores element e)
+    double v = s[0];
+#pragma unroll
+    for (int e = 1; e < 9; ++e)
+        if (lane == e) v = s[e];
+    if (lane < 9) {
+        const int r = lane / 3, c = lane % 3;
+        if (P.o >= 0) out[P.o + r * ld + c] = v;
+        if (P.ot >= 0) out[P.ot + c * ld + r] = v;
+    }
+}
+
 // device buffers are kept between rebuilds of the same solver (an incremental graph re-derives its
 // structures every update): a buffer is re-allocated only when it must grow (by 1.5x at least)
 template <typename T>
@@ -2214,6 +2355,15 @@ struct CholDev {
     std::vector<size_t> sel_lds;  // per level: dynamic LDS bytes of its launch
     std::vector<SelPick> h_picks;
     std::vector<hipEvent_t> sel_ev;
+    // joint marginals (dpg_chol_joint): its own plan and buffers, allocated by the first request and
+    // regrown only when a request needs more; nothing above is written
+    JointPlan jplan;
+    double* jt_w = nullptr;       // the compact W buffer (the queries' slices)
+    double* jt_work = nullptr;    // the path solve's vectors when they do not fit LDS
+    double* jt_out = nullptr;
+    char* jt_lists = nullptr;     // [PathPair pairs | PathQuery queries]
+    size_t c_jt_w = 0, c_jt_work = 0, c_jt_out = 0, c_jt_lists = 0;
+    hipEvent_t jt_ev[3] = {nullptr, nullptr, nullptr};
 };
 
 // a new analysis in; *S gets back one whose buffers the caller reuses.  With tracking, the analysis
@@ -2236,8 +2386,10 @@ extern "C" void dpg_chol_destroy(void* h) {
     // (the structure arrays live in c->arena)
     if (c->aux) (void)hipStreamSynchronize(c->aux);
     void* ptrs[] = {c->arena, c->fronts, c->acc, c->ysol, c->xsol, c->status, c->sync, c->dinv, c->linv, c->scratch, c->dpart,
-                    c->sel, c->sel_work, c->sel_out, c->sel_lists, c->sel_picks};
+                    c->sel, c->sel_work, c->sel_out, c->sel_lists, c->sel_picks, c->jt_w, c->jt_work, c->jt_out, c->jt_lists};
     for (hipEvent_t e : c->sel_ev) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->jt_ev)
+        if (e) (void)hipEventDestroy(e);
     if (c->pev) (void)hipEventDestroy(c->pev);
     if (c->pstage) (void)hipHostFree(c->pstage);
     for (void* p : ptrs)
@@ -2986,6 +3138,82 @@ extern "C" int dpg_chol_marginals(void* h, const int32_t* nodes, int64_t n, cons
 extern "C" int64_t dpg_chol_selinv_bytes(void* h) {
     const CholDev* c = reinterpret_cast<const CholDev*>(h);
     return c ? (int64_t)(sizeof(double) * (c->c_sel + c->c_sel_work)) : 0;
+}
+
+// ---- joint marginals: host side ----
+// Blocks of Sigma for any nodes from the factor h holds now (only read): by_nodes = 0 -- idx is
+// pairs[n][2] and host_out[n][9] gets Sigma(i, j) row-major; by_nodes = 1 -- idx is nodes[n] and
+// host_out[3n][3n] gets their joint covariance.  ms (may be NULL): the path solve's and the dot
+// kernel's time from HIP events.  Nothing is written to host_out unless everything succeeded.
+extern "C" int dpg_chol_joint(void* h, int by_nodes, const int32_t* idx, int64_t n, double* host_out, void* stream,
+                              float* ms) {
+    CholDev* c = reinterpret_cast<CholDev*>(h);
+    if (!c) return DPG_ERR_STATE;
+    const dpg_chol_sym& S = c->sym;
+    if (n < 0 || (n > 0 && (!idx || !host_out))) return DPG_ERR_ARG;
+    for (int64_t q = 0, e = by_nodes ? n : 2 * n; q < e; ++q)
+        if (idx[q] < 0 || idx[q] >= S.n) return DPG_ERR_ARG;
+    if (!c->has_factor) return DPG_ERR_STATE;
+    if (ms) ms[0] = ms[1] = 0.f;
+    if (n == 0) return DPG_OK;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    JointPlan& J = c->jplan;
+    if (by_nodes) dpg_chol_plan_joint_nodes(J, S, idx, n);
+    else dpg_chol_plan_joint_pairs(J, S, idx, n);
+    const int64_t nq = (int64_t)J.queries.size(), np = (int64_t)J.pairs.size();
+    const int ldv = path_ldv(S.max_front);
+    const bool in_lds = path_in_lds(S.max_front);
+    const unsigned grid = (unsigned)std::min<int64_t>(nq, kPathGrid);
+    const size_t pb = sizeof(PathPair) * (size_t)np, qb = sizeof(PathQuery) * (size_t)nq;
+    // (the lists are rewritten per request: an earlier request's kernels must be done with them)
+    if (hipStreamSynchronize(st) != hipSuccess || dreserve(&c->jt_w, &c->c_jt_w, (size_t)J.w_total) ||
+        dreserve(&c->jt_work, &c->c_jt_work, in_lds ? 1 : (size_t)grid * 6 * (size_t)ldv) ||
+        dreserve(&c->jt_out, &c->c_jt_out, (size_t)J.out_total) || dreserve(&c->jt_lists, &c->c_jt_lists, pb + qb) ||
+        hipMemcpy(c->jt_lists, J.pairs.data(), pb, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(c->jt_lists + pb, J.queries.data(), qb, hipMemcpyHostToDevice) != hipSuccess)
+        return DPG_ERR_HIP;
+    if (ms)
+        for (hipEvent_t& e : c->jt_ev)
+            if (!e && hipEventCreate(&e) != hipSuccess) return DPG_ERR_HIP;
+    const PathPair* pairs = reinterpret_cast<const PathPair*>(c->jt_lists);
+    const PathQuery* queries = reinterpret_cast<const PathQuery*>(c->jt_lists + pb);
+    if (ms && hipEventRecord(c->jt_ev[0], st) != hipSuccess) return DPG_ERR_HIP;
+    hipLaunchKernelGGL(chol_path_forward, dim3(grid), dim3(kT), in_lds ? sizeof(double) * 6 * (size_t)ldv : 0, st, queries, nq,
+                       c->sns, c->relmap, c->fronts, c->jt_w, c->jt_work, ldv, in_lds ? 1 : 0);
+    if (ms && hipEventRecord(c->jt_ev[1], st) != hipSuccess) return DPG_ERR_HIP;
+    hipLaunchKernelGGL(chol_path_dot, dim3((unsigned)((np + 3) / 4)), dim3(256), 0, st, pairs, np, c->jt_w, c->jt_out,
+                       (int64_t)J.ld);
+    if (ms && hipEventRecord(c->jt_ev[2], st) != hipSuccess) return DPG_ERR_HIP;
+    if (hipGetLastError() != hipSuccess) return DPG_ERR_HIP;
+    std::vector<double> tmp((size_t)J.out_total);
+    int32_t status = 0;
+    if (hipMemcpyAsync(&status, c->status, sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(tmp.data(), c->jt_out, sizeof(double) * tmp.size(), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return DPG_ERR_HIP;
+    if (status != 0) return DPG_ERR_NUMERIC;
+    for (double v : tmp)
+        if (!(v == v)) return DPG_ERR_NUMERIC;
+    if (ms && (hipEventElapsedTime(ms, c->jt_ev[0], c->jt_ev[1]) != hipSuccess ||
+               hipEventElapsedTime(ms + 1, c->jt_ev[1], c->jt_ev[2]) != hipSuccess))
+        return DPG_ERR_HIP;
+    memcpy(host_out, tmp.data(), sizeof(double) * tmp.size());
+    return DPG_OK;
+}
+
+// the longest root path among the analysis's nodes: {fronts, pivot scalars}
+extern "C" void dpg_chol_path_stats(void* h, int64_t out[2]) {
+    const dpg_chol_sym& S = reinterpret_cast<CholDev*>(h)->sym;
+    out[0] = out[1] = 0;
+    for (int32_t s0 = 0; s0 < S.ns; ++s0) {
+        int64_t nf = 0, len = 0;
+        for (int32_t s = s0; s >= 0; s = S.sn_parent[(size_t)s]) {
+            ++nf;
+            len += 3 * (S.sn_c0[(size_t)s + 1] - S.sn_c0[(size_t)s]);
+        }
+        out[0] = std::max(out[0], nf);
+        out[1] = std::max(out[1], len);
+    }
 }
 
 #ifdef DPG_CHOL_TIMING

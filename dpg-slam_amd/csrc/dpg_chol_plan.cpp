@@ -598,6 +598,88 @@ int dpg_chol_plan_build(CholPlan& P, const dpg_chol_sym& S, const dpg_chol_opts&
     return DPG_OK;
 }
 
+// ---- joint marginals: root paths, W slices and per-block suffixes ----
+namespace {
+
+void joint_begin(JointPlan& J, const dpg_chol_sym& S) {
+    J.nodes.clear();
+    J.queries.clear();
+    J.path_ptr.assign(1, 0);
+    J.path_sn.clear();
+    J.path_len.clear();
+    J.len.clear();
+    J.pairs.clear();
+    J.w_total = 0;
+    J.slot.assign((size_t)S.n, -1);
+}
+
+// the query of node v (a new one walks sn_parent from v's front to its root)
+int32_t joint_query(JointPlan& J, const dpg_chol_sym& S, int32_t v) {
+    if (J.slot[(size_t)v] >= 0) return J.slot[(size_t)v];
+    const int32_t q = (int32_t)J.nodes.size();
+    const int32_t p = S.pos[(size_t)v];
+    const int32_t s0 = S.sn_of[(size_t)p];
+    int64_t len = 0;
+    for (int32_t s = s0; s >= 0; s = S.sn_parent[(size_t)s]) {
+        const int32_t k3 = 3 * (S.sn_c0[(size_t)s + 1] - S.sn_c0[(size_t)s]);
+        J.path_sn.push_back(s);
+        J.path_len.push_back(k3);
+        len += k3;
+    }
+    J.path_ptr.push_back((int64_t)J.path_sn.size());
+    J.nodes.push_back(v);
+    J.queries.push_back(PathQuery{s0, 3 * (p - S.sn_c0[(size_t)s0]), J.w_total});
+    J.len.push_back(len);
+    J.w_total += 3 * len;
+    J.slot[(size_t)v] = q;
+    return q;
+}
+
+// block Sigma(u, v) to o and its transpose to ot (either may be -1).  The product is taken with
+// the smaller node's slice on the left, so (u, v) and (v, u) are one computation and its mirror.
+void joint_block(JointPlan& J, const dpg_chol_sym& S, int32_t u, int32_t v, int64_t o, int64_t ot) {
+    if (u > v) {
+        std::swap(u, v);
+        std::swap(o, ot);
+    }
+    const int32_t qa = joint_query(J, S, u), qb = joint_query(J, S, v);
+    // the common suffix of the two paths: equal fronts from the roots' end
+    int64_t ea = J.path_ptr[(size_t)qa + 1], eb = J.path_ptr[(size_t)qb + 1];
+    const int64_t ba = J.path_ptr[(size_t)qa], bb = J.path_ptr[(size_t)qb];
+    int64_t len = 0;
+    while (ea > ba && eb > bb && J.path_sn[(size_t)ea - 1] == J.path_sn[(size_t)eb - 1]) {
+        len += J.path_len[(size_t)ea - 1];
+        --ea;
+        --eb;
+    }
+    PathPair t;
+    t.a = J.queries[(size_t)qa].w_off + 3 * (J.len[(size_t)qa] - len);
+    t.b = J.queries[(size_t)qb].w_off + 3 * (J.len[(size_t)qb] - len);
+    t.o = o;
+    t.ot = ot;
+    t.len = (int32_t)len;
+    t.pad = 0;
+    J.pairs.push_back(t);
+}
+
+}  // namespace
+
+void dpg_chol_plan_joint_pairs(JointPlan& J, const dpg_chol_sym& S, const int32_t* pairs, int64_t n) {
+    joint_begin(J, S);
+    J.ld = 3;
+    J.out_total = 9 * n;
+    for (int64_t q = 0; q < n; ++q) joint_block(J, S, pairs[2 * q], pairs[2 * q + 1], 9 * q, -1);
+}
+
+void dpg_chol_plan_joint_nodes(JointPlan& J, const dpg_chol_sym& S, const int32_t* nodes, int64_t n) {
+    joint_begin(J, S);
+    J.ld = (int32_t)(3 * n);
+    J.out_total = 9 * n * n;
+    for (int64_t p = 0; p < n; ++p)
+        for (int64_t q = p; q < n; ++q)
+            joint_block(J, S, nodes[p], nodes[q], 3 * p * J.ld + 3 * q, q > p ? 3 * q * J.ld + 3 * p : -1);
+}
+
 }  // namespace dpg_chol
 
 #ifdef DPG_PLAN_TIMING

@@ -188,6 +188,44 @@ void dpg_chol_plan_prebucket(CholPlan& P, int64_t n, const int32_t* pos, const i
 int dpg_chol_plan_build(CholPlan& P, const dpg_chol_sym& S, const dpg_chol_opts& o, bool track, int64_t n,
                         const int32_t* pair_lo, const int32_t* pair_hi, int64_t n_pairs);
 
+// ---- joint marginals: blocks of Sigma anywhere, from root paths of the factor (dpg_chol_joint) ----
+// W_q = L^-1 E_q (E_q: the three unit columns of node q) is nonzero only on the pivot rows of the
+// fronts from q's own to the root of its tree.  A query's slice of the compact W buffer holds
+// those rows, front after front in path order, row-major [scalars][3]; two root paths share a
+// suffix of equal length in both slices (from the lowest common front to the root; nothing when
+// the nodes lie in different trees), and Sigma(i, j) is the 3x3 product of the two suffixes.
+constexpr int kPB = 24;          // pivot block of the path solve (scalar columns)
+constexpr int kPathLds = 2048;   // doubles: the path solve keeps its two vectors in LDS up to here (16 KiB)
+constexpr int kPathGrid = 1024;  // workgroups of the path solve at most (each takes every kPathGrid-th query)
+// rows per right-hand side of the path solve's vectors, and whether the two [3][ldv] vectors fit LDS
+inline int path_ldv(int32_t max_front) { return (3 * max_front + 1) & ~1; }
+inline bool path_in_lds(int32_t max_front) { return 6 * path_ldv(max_front) <= kPathLds; }
+
+struct PathQuery { int32_t sn, row; int64_t w_off; };   // first front, the node's first scalar row in it, slice (doubles)
+// one 3x3 block: the suffixes' starts in W (doubles) and their length in scalars; the block goes to
+// out[o + r ld + c] (o >= 0) and its transpose to out[ot + c ld + r] (ot >= 0)
+struct PathPair { int64_t a, b, o, ot; int32_t len, pad; };
+static_assert(sizeof(PathQuery) == 16 && sizeof(PathPair) == 40 && alignof(PathPair) == 8, "record layout");
+
+struct JointPlan {
+    std::vector<int32_t> nodes;        // the distinct queried nodes, in order of first appearance
+    std::vector<PathQuery> queries;    // parallel to nodes
+    std::vector<int64_t> path_ptr;     // [nodes + 1] into path_sn / path_len
+    std::vector<int32_t> path_sn;      // the fronts of each path, the node's own first
+    std::vector<int32_t> path_len;     // their pivot scalars
+    std::vector<int64_t> len;          // scalars of each path (the slice holds 3 len doubles)
+    std::vector<PathPair> pairs;
+    int64_t w_total = 0;               // doubles of the W buffer
+    int64_t out_total = 0;             // doubles of the output
+    int32_t ld = 3;                    // leading dimension of the output's blocks
+    std::vector<int32_t> slot;         // scratch: node -> index in nodes, -1
+};
+// Sigma(pairs[q][0], pairs[q][1]) -> out[q][9] row-major.  Nodes must be in range (the caller checks).
+void dpg_chol_plan_joint_pairs(JointPlan& J, const dpg_chol_sym& S, const int32_t* pairs, int64_t n);
+// the joint covariance of nodes[0 .. n) -> out[3n][3n] row-major: every block on or above the block
+// diagonal once, mirrored below
+void dpg_chol_plan_joint_nodes(JointPlan& J, const dpg_chol_sym& S, const int32_t* nodes, int64_t n);
+
 }  // namespace dpg_chol
 
 #endif

@@ -193,3 +193,51 @@ int64_t dpg_scans_to_clouds(const float* ranges, int64_t n_nodes, int64_t n_beam
     }
     return total;
 }
+
+/* Covariance of the relative pose z = X_i^-1 X_j in z's own tangent frame: to first order
+ * dz = A_i d_i + d_j with A_i = -Ad(z^-1), the Jacobians of the Between linearization at zero error
+ * (BetweenFactor::evaluateError of GTSAM 4.x: H1 = -z^-1.AdjointMap(), H2 = I), so
+ *   cov = A_i Sii A_i^T + A_i Sij + (A_i Sij)^T + Sjj.
+ * All blocks row-major; the result is exactly symmetric (the upper triangle mirrored). */
+void dpg_relative_covariance(const double xi[3], const double xj[3], const double* Sii, const double* Sij,
+                             const double* Sjj, double out[9]) {
+    const double d = xj[2] - xi[2], c = cos(d), s = sin(d);
+    const double cj = cos(xj[2]), sj = sin(xj[2]);
+    const double dx = xj[0] - xi[0], dy = xj[1] - xi[1];
+    const double A[9] = {-c, -s, -sj * dx + cj * dy, s, -c, -cj * dx - sj * dy, 0.0, 0.0, -1.0};
+    double AS[9], N[9];
+    for (int r = 0; r < 3; ++r)
+        for (int q = 0; q < 3; ++q) {
+            double u = 0.0, v = 0.0;
+            for (int k = 0; k < 3; ++k) {
+                u += A[3 * r + k] * Sii[3 * k + q];
+                v += A[3 * r + k] * Sij[3 * k + q];
+            }
+            AS[3 * r + q] = u;
+            N[3 * r + q] = v;
+        }
+    for (int r = 0; r < 3; ++r)
+        for (int q = r; q < 3; ++q) {
+            double m = 0.0;
+            for (int k = 0; k < 3; ++k) m += AS[3 * r + k] * A[3 * q + k];
+            out[3 * r + q] = out[3 * q + r] = m + (N[3 * r + q] + N[3 * q + r]) + 0.5 * (Sjj[3 * r + q] + Sjj[3 * q + r]);
+        }
+}
+
+void dpg_relative_triples(const int32_t* pairs, int64_t n, int32_t* tri) {
+    for (int64_t q = 0; q < n; ++q) {
+        const int32_t i = pairs[2 * q], j = pairs[2 * q + 1];
+        int32_t* t = tri + 6 * q;
+        t[0] = t[1] = t[2] = i;
+        t[3] = t[4] = t[5] = j;
+    }
+}
+
+void dpg_relative_from_blocks(const int32_t* pairs, int64_t n, const double* X, const double* blocks, double* out) {
+    for (int64_t q = 0; q < n; ++q) {
+        const int32_t i = pairs[2 * q], j = pairs[2 * q + 1];
+        const double* B = blocks + 27 * q;
+        if (i == j) memset(out + 9 * q, 0, 9 * sizeof(double));
+        else dpg_relative_covariance(X + 3 * i, X + 3 * j, B, B + 9, B + 18, out + 9 * q);
+    }
+}

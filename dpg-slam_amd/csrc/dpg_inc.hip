@@ -1064,4 +1064,62 @@ int dpg_inc_marginals(dpg_inc* q, const int32_t* nodes, int64_t n, double* cov_o
     return DPG_OK;
 }
 
+// Marginals::jointMarginalCovariance on the incremental graph: blocks of Sigma for any nodes from
+// root paths of the factor the last update left (dpg_chol_joint; read only, as above)
+static int inc_joint_err(const char* fn, int rc, const char* what) {
+    char msg[200];
+    snprintf(msg, sizeof msg, "%s: %s", fn, what);
+    return set_err(rc, msg);
+}
+
+// host only: the graph holds a factor to read and the request is well formed
+static int inc_joint_check(dpg_inc* q, const char* fn, int by_nodes, const int32_t* idx, int64_t n, const double* out) {
+    if (!q || !q->g.chol || q->V == 0 || q->updates == 0)
+        return inc_joint_err(fn, DPG_ERR_STATE, "the graph holds no factorization yet");
+    if (dpg_ctx_is_multi(q->ctx)) return inc_joint_err(fn, DPG_ERR_STATE, "marginals are single-device");
+    if (q->prepared)
+        return inc_joint_err(fn, DPG_ERR_STATE, "an update is prepared (its analysis has replaced the factor's)");
+    if (n < 0 || (n > 0 && (!idx || !out))) return inc_joint_err(fn, DPG_ERR_ARG, "bad arguments");
+    for (int64_t k = 0, e = by_nodes ? n : 2 * n; k < e; ++k)
+        if (idx[k] < 0 || idx[k] >= q->V) return inc_joint_err(fn, DPG_ERR_ARG, "a node is out of range");
+    return DPG_OK;
+}
+
+static int inc_joint_blocks(dpg_inc* q, const char* fn, int by_nodes, const int32_t* idx, int64_t n, double* out) {
+    int rc = inc_joint_check(q, fn, by_nodes, idx, n, out);
+    if (rc || n == 0) return rc;
+    if (hipSetDevice(dpg_ctx_device_of(q->ctx)) != hipSuccess) return set_err(DPG_ERR_HIP, "hipSetDevice failed");
+    rc = dpg_chol_joint(q->g.chol, by_nodes, idx, n, out, dpg_ctx_stream_of(q->ctx), nullptr);
+    if (rc == DPG_ERR_STATE) return inc_joint_err(fn, rc, "the graph holds no factorization (failed or restored update)");
+    if (rc == DPG_ERR_NUMERIC) return inc_joint_err(fn, rc, "H is not positive definite");
+    if (rc) return inc_joint_err(fn, rc, "the path solve failed");
+    return DPG_OK;
+}
+
+int dpg_inc_cross_covariances(dpg_inc* q, const int32_t* pairs, int64_t n, double* cov_out) {
+    return inc_joint_blocks(q, "dpg_inc_cross_covariances", 0, pairs, n, cov_out);
+}
+
+int dpg_inc_joint_marginal(dpg_inc* q, const int32_t* nodes, int64_t n, double* cov_out) {
+    return inc_joint_blocks(q, "dpg_inc_joint_marginal", 1, nodes, n, cov_out);
+}
+
+// the relative-pose Jacobian at theta, the point the factor was linearized at
+int dpg_inc_relative_covariances(dpg_inc* q, const int32_t* pairs, int64_t n, double* cov_out) {
+    const char* fn = "dpg_inc_relative_covariances";
+    int rc = inc_joint_check(q, fn, 0, pairs, n, cov_out);
+    if (rc || n == 0) return rc;
+    std::vector<int32_t> tri((size_t)(6 * n));
+    dpg_relative_triples(pairs, n, tri.data());
+    std::vector<double> blocks((size_t)(27 * n));
+    if ((rc = inc_joint_blocks(q, fn, 0, tri.data(), 3 * n, blocks.data()))) return rc;
+    std::vector<double> X((size_t)(3 * q->V));
+    hipStream_t s = reinterpret_cast<hipStream_t>(dpg_ctx_stream_of(q->ctx));
+    if (hipMemcpyAsync(X.data(), q->theta, sizeof(double) * X.size(), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return set_err(DPG_ERR_HIP, "dpg_inc_relative_covariances: copy failed");
+    dpg_relative_from_blocks(pairs, n, X.data(), blocks.data(), cov_out);
+    return DPG_OK;
+}
+
 }  // extern "C"

@@ -209,6 +209,25 @@ int dpg_chol_selinv_gather(void* chol, const int32_t* nodes, int64_t n, const in
 int dpg_chol_marginals(void* chol, const int32_t* nodes, int64_t n, const int32_t* pairs, int64_t n_pairs,
                        double* host_out, void* stream);
 int64_t dpg_chol_selinv_bytes(void* chol);   /* Sigma + work buffers, bytes */
+/* Joint marginals: blocks of Sigma for ANY nodes (also outside L's pattern) from the factor chol
+   holds now, by one forward substitution along each queried node's root path and dot products over
+   the part two paths share (its own buffers, allocated on the first request; the factor, the
+   solves' state and the selected inverse are only read).  by_nodes = 0: idx = pairs[n][2],
+   host_out[n][9] row-major; by_nodes = 1: idx = nodes[n], host_out[3n][3n] row-major, exactly
+   symmetric.  ms (may be NULL): {path solve, dot} from HIP events.  DPG_ERR_ARG -- a node out of
+   range, NULL with n > 0, n < 0; DPG_ERR_STATE without a factor; DPG_ERR_NUMERIC when the
+   factorization failed; host_out is written only on success */
+int dpg_chol_joint(void* chol, int by_nodes, const int32_t* idx, int64_t n, double* host_out, void* stream, float* ms);
+void dpg_chol_path_stats(void* chol, int64_t out[2]);   /* longest root path: fronts, pivot scalars */
+/* The covariance of z = X_i^-1 X_j in z's tangent frame from the row-major blocks Sii, Sij, Sjj at
+   the poses xi, xj: J [[Sii, Sij], [Sij^T, Sjj]] J^T, J = [A_i I] the Between linearization at zero
+   error (dpg_host.c) */
+void dpg_relative_covariance(const double xi[3], const double xj[3], const double* Sii, const double* Sij,
+                             const double* Sjj, double out[9]);
+/* per pair (i, j): the block requests (i, i), (i, j), (j, j) into tri[3n][2]; and, from those
+   blocks[n][3][9] and the poses X, the relative covariances out[n][9] (zeros where i == j) */
+void dpg_relative_triples(const int32_t* pairs, int64_t n, int32_t* tri);
+void dpg_relative_from_blocks(const int32_t* pairs, int64_t n, const double* X, const double* blocks, double* out);
 
 /* host work first (pattern, lists, the Cholesky's analysis and plan), then -- after
    hipStreamSynchronize(sync_stream) when given -- the device allocations and uploads */

@@ -311,6 +311,10 @@ SIGNATURES = {
     "dpg_gn_last_solve_ms": (C.c_float, [P]),
     "dpg_gn_marginals": (C.c_int, [P, I32P, C.c_int64, F64P]),
     "dpg_gn_marginal_pairs": (C.c_int, [P, I32P, C.c_int64, F64P]),
+    "dpg_gn_cross_covariances": (C.c_int, [P, I32P, C.c_int64, F64P]),
+    "dpg_gn_joint_marginal": (C.c_int, [P, I32P, C.c_int64, F64P]),
+    "dpg_gn_relative_covariances": (C.c_int, [P, I32P, C.c_int64, F64P]),
+    "dpg_gn_joint_profile": (C.c_int, [P, I32P, C.c_int64, F64P, C.c_int64]),
     "dpg_marginal_covariances": (C.c_int, [P, F64P, C.c_int64, P, C.c_int64, I32P, C.c_int64, F64P]),
     "dpg_gn_marginals_profile": (C.c_int64, [P, F64P, C.c_int64]),
     "icp_cov_calculate": (C.c_int, [P, F32P, C.c_int64, F32P, C.c_int64, F32P, C.c_float, C.c_float,
@@ -341,6 +345,9 @@ SIGNATURES = {
     "dpg_inc_num_nodes": (C.c_int64, [P]),
     "dpg_inc_get_poses": (C.c_int, [P, F64P, C.c_int64]),
     "dpg_inc_marginals": (C.c_int, [P, I32P, C.c_int64, F64P]),
+    "dpg_inc_cross_covariances": (C.c_int, [P, I32P, C.c_int64, F64P]),
+    "dpg_inc_joint_marginal": (C.c_int, [P, I32P, C.c_int64, F64P]),
+    "dpg_inc_relative_covariances": (C.c_int, [P, I32P, C.c_int64, F64P]),
     "dpg_inc_save": (C.c_int, [P, C.c_char_p]),
     "dpg_inc_load": (P, [P, C.c_char_p]),
     "dpg_inc_export": (C.c_int64, [P, I64P, P, I32P, C.c_int64, F64P, F64P, F64P]),

@@ -59,6 +59,24 @@ def _pair_list(pairs):
     return np.ascontiguousarray(a, np.int32)
 
 
+def _joint_pairs(name, handle, pairs):
+    """name(handle, pairs[n][2], n, out[n][9]) of the joint-marginal entry points -> [n, 3, 3]."""
+    pr = _pair_list(pairs)
+    out = np.empty((len(pr), 3, 3), np.float64)
+    check(getattr(lib(), name)(handle, ptr(pr, C.c_int32), len(pr), ptr(out, C.c_double)), name)
+    return out
+
+
+def _joint_nodes(name, handle, nodes):
+    """name(handle, nodes[n], n, out[3n][3n]) -> [3n, 3n]."""
+    nd = _node_list(nodes)
+    if nd is None:
+        raise ValueError("nodes: expected a 1-D sequence of node indices, got None")
+    out = np.empty((3 * len(nd), 3 * len(nd)), np.float64)
+    check(getattr(lib(), name)(handle, ptr(nd, C.c_int32), len(nd), ptr(out, C.c_double)), name)
+    return out
+
+
 # ------------------------------------------------------------------------- host helpers (R1-R3)
 def scan_to_cloud(ranges, angle_min, angle_max, range_max, laser=(0.2, 0.0, 0.0)) -> np.ndarray:
     r = _f32(ranges)
@@ -442,6 +460,28 @@ class Context:
               "dpg_gn_marginal_pairs")
         return out
 
+    # ---- joint marginals of any nodes (Marginals::jointMarginalCovariance) ----
+    def gn_cross_covariances(self, pairs) -> np.ndarray:
+        """dpg_gn_cross_covariances: Sigma(i, j) for any node pairs, sharing a factor or not; [n, 3, 3]."""
+        return _joint_pairs("dpg_gn_cross_covariances", self.handle, pairs)
+
+    def gn_joint_marginal(self, nodes) -> np.ndarray:
+        """dpg_gn_joint_marginal: the joint covariance over `nodes` in their order; [3n, 3n]."""
+        return _joint_nodes("dpg_gn_joint_marginal", self.handle, nodes)
+
+    def gn_relative_covariances(self, pairs) -> np.ndarray:
+        """dpg_gn_relative_covariances: the covariance of X_i^-1 X_j in its own tangent frame; [n, 3, 3]."""
+        return _joint_pairs("dpg_gn_relative_covariances", self.handle, pairs)
+
+    def gn_joint_profile(self, pairs) -> dict:
+        """dpg_gn_joint_profile: one gn_cross_covariances call with its two kernels timed by HIP events."""
+        pr = _pair_list(pairs)
+        out = np.zeros(4, np.float64)
+        check(lib().dpg_gn_joint_profile(self.handle, ptr(pr, C.c_int32), len(pr), ptr(out, C.c_double), len(out)),
+              "dpg_gn_joint_profile")
+        return {"path_ms": float(out[0]), "dot_ms": float(out[1]), "path_fronts": int(out[2]),
+                "path_scalars": int(out[3])}
+
     def gn_marginals_profile(self) -> dict:
         """dpg_gn_marginals_profile: one all-node marginals call with its parts timed by HIP events."""
         out = np.zeros(4 + 4096, np.float64)
@@ -744,6 +784,18 @@ class IncGraph:
         check(lib().dpg_inc_marginals(self.handle, ptr(nd, C.c_int32) if nd is not None else None, n,
                                       ptr(out, C.c_double)), "dpg_inc_marginals")
         return out
+
+    def cross_covariances(self, pairs) -> np.ndarray:
+        """dpg_inc_cross_covariances: Sigma(i, j) for any node pairs from the factor as it stands; [n, 3, 3]."""
+        return _joint_pairs("dpg_inc_cross_covariances", self.handle, pairs)
+
+    def joint_marginal(self, nodes) -> np.ndarray:
+        """dpg_inc_joint_marginal: the joint covariance over `nodes` in their order; [3n, 3n]."""
+        return _joint_nodes("dpg_inc_joint_marginal", self.handle, nodes)
+
+    def relative_covariances(self, pairs) -> np.ndarray:
+        """dpg_inc_relative_covariances: the covariance of X_i^-1 X_j in its own tangent frame; [n, 3, 3]."""
+        return _joint_pairs("dpg_inc_relative_covariances", self.handle, pairs)
 
     def save(self, path: str):
         """dpg_inc_save: the graph and its context's scan store to one checkpoint file."""

@@ -82,6 +82,10 @@ class GpuBackend:
         """ISAM2::marginalCovariance of the graph as it stands (dpg_inc_marginals): [n, 3, 3]."""
         return self.inc.marginals(nodes)
 
+    def relative_covariances(self, pairs):
+        """The covariance of X_i^-1 X_j per node pair (dpg_inc_relative_covariances): [n, 3, 3]."""
+        return self.inc.relative_covariances(pairs)
+
     def store(self, ranges, geom, offsets, params):
         return api.DpgStore(self.ctx, ranges, geom, offsets=offsets, params=params)
 
@@ -193,6 +197,24 @@ class DpgSLAM:
             raise NotImplementedError(f"GetPoseCovariance needs a `marginals(nodes)` method on the backend; "
                                       f"{type(self.be).__name__} has none")
         return np.asarray(fn([k]), np.float64).reshape(3, 3)
+
+    def GetRelativePoseCovariance(self, i, j):
+        """The 3x3 covariance of the relative pose X_i^-1 X_j between two nodes of the graph, in
+        that relative pose's own tangent frame -- what a covariance gate of a loop-closure candidate
+        (i, j) reads before an ICP alignment is spent on it; the nodes need not share a factor
+        (gtsam::Marginals::jointMarginalCovariance and the Between Jacobians).  Zero for i == j."""
+        V = len(self.poses)
+        if V == 0:
+            raise ValueError("GetRelativePoseCovariance: the graph has no node yet")
+        i, j = int(i), int(j)
+        for k in (i, j):
+            if not 0 <= k < V:
+                raise IndexError(f"GetRelativePoseCovariance: node {k} out of range (the graph has {V} nodes)")
+        fn = getattr(self.be, "relative_covariances", None)
+        if fn is None:
+            raise NotImplementedError(f"GetRelativePoseCovariance needs a `relative_covariances(pairs)` method on "
+                                      f"the backend; {type(self.be).__name__} has none")
+        return np.asarray(fn([(i, j)]), np.float64).reshape(3, 3)
 
     def GetMap(self):
         """dpg_slam.cc:555-575."""

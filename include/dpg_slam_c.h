@@ -422,6 +422,33 @@ int dpg_gn_marginals(dpg_ctx* ctx, const int32_t* nodes, int64_t n, double* cov_
 /* joint blocks Sigma(i, j) (rows i, columns j) for pairs that share a factor; Sigma(j, i) is its
  * transpose */
 int dpg_gn_marginal_pairs(dpg_ctx* ctx, const int32_t* pairs /*[n][2]*/, int64_t n, double* cov_out /*[n][9]*/);
+/* ---- joint marginals of any nodes (gtsam::Marginals::jointMarginalCovariance) ----
+ * Blocks of Sigma for ANY nodes, sharing a factor or not: with P H P^T = L L^T,
+ * Sigma(i, j) = (L^-1 E_i)^T (L^-1 E_j), E_q the three unit columns of node q.  L^-1 E_q is nonzero
+ * only on the fronts between q's and the root of its elimination tree, so a query is one forward
+ * substitution along one root path plus dot products over the part two paths share (DESIGN.md,
+ * "Joint marginals").  Tangent frames, the linearization point, "does not change the poses, the
+ * step history or the factorization count" and the DPG_ERR_STATE / DPG_ERR_NUMERIC cases are those
+ * of dpg_gn_marginals; DPG_ERR_ARG -- a node out of range, a NULL list with n > 0, n < 0.  cov_out
+ * is not written on any error.  All solver options are supported (solve_inv_cols keeps L11^-1 in a
+ * buffer of its own: the fronts still hold L11).  dpg_gn_marginal_pairs is unchanged: it still
+ * refuses pairs without a common factor. */
+/* Sigma(i, j) (rows i, columns j) for any i, j in range -- i == j, repeated nodes and repeated
+ * pairs included; the block of (j, i) is bitwise the transpose of the block of (i, j) */
+int dpg_gn_cross_covariances(dpg_ctx* ctx, const int32_t* pairs /*[n][2]*/, int64_t n, double* cov_out /*[n][9]*/);
+/* jointMarginalCovariance(nodes): the full covariance over `nodes` in the caller's order, exactly
+ * symmetric (each block computed once and mirrored) */
+int dpg_gn_joint_marginal(dpg_ctx* ctx, const int32_t* nodes, int64_t n, double* cov_out /*[3n][3n] row-major*/);
+/* The 3x3 covariance of the relative pose z = X_i^-1 X_j in z's own tangent frame:
+ * J [[Sii, Sij], [Sji, Sjj]] J^T, J = [A_i A_j] the Jacobians of the Between linearization at zero
+ * error (A_j = I, A_i = -Ad(z^-1)), taken at the poses Sigma was computed at.  Exactly symmetric;
+ * the zero matrix for i == j.  With the candidate's measured z_m, e = Local(z, z_m) and
+ * e^T (cov + cov_m)^-1 e is the Mahalanobis gate of a loop-closure candidate. */
+int dpg_gn_relative_covariances(dpg_ctx* ctx, const int32_t* pairs /*[n][2]*/, int64_t n, double* cov_out /*[n][9]*/);
+/* Diagnostic (tools/joint_probe.py): one dpg_gn_cross_covariances with its kernels timed by HIP
+ * events.  out = {path solve ms, dot ms, the longest root path of the analysis in fronts, in pivot
+ * scalars}; cap >= 4. */
+int dpg_gn_joint_profile(dpg_ctx* ctx, const int32_t* pairs /*[n][2]*/, int64_t n, double* out, int64_t cap);
 /* one call: set up the graph (default parameters; it becomes the context's graph), linearize at
  * poses, factor, invert */
 int dpg_marginal_covariances(dpg_ctx* ctx, const double* poses, int64_t n_nodes, const dpg_factor* factors,
@@ -566,6 +593,13 @@ int dpg_inc_get_poses(dpg_inc* g, double* poses, int64_t n);
  * DPG_ERR_STATE also: before the first update, after a failed update or dpg_inc_load until the
  * next successful update. */
 int dpg_inc_marginals(dpg_inc* g, const int32_t* nodes, int64_t n, double* cov_out /*[n][9]*/);
+/* dpg_gn_cross_covariances / dpg_gn_joint_marginal / dpg_gn_relative_covariances on the incremental
+ * graph's factor as it stands: the conventions, the read-only guarantee and the errors of
+ * dpg_inc_marginals (DPG_ERR_ARG also for a NULL list with n > 0).  The relative-pose Jacobian is
+ * taken at theta, the point the factor was linearized at. */
+int dpg_inc_cross_covariances(dpg_inc* g, const int32_t* pairs /*[n][2]*/, int64_t n, double* cov_out /*[n][9]*/);
+int dpg_inc_joint_marginal(dpg_inc* g, const int32_t* nodes, int64_t n, double* cov_out /*[3n][3n] row-major*/);
+int dpg_inc_relative_covariances(dpg_inc* g, const int32_t* pairs /*[n][2]*/, int64_t n, double* cov_out /*[n][9]*/);
 
 /* Graph checkpoint ("optional binary dump of the graph (poses, edges,
  * measurements)"; the reference keeps dpg_nodes_ with their scans, graph_ and isam_ only in memory,
