@@ -32,7 +32,6 @@
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
-#include <time.h>
 
 #include <algorithm>
 #include <cmath>
@@ -40,7 +39,7 @@
 #include <vector>
 
 #include "dpg_atan2f.h"
-#include "dpg_internal.h"
+#include "dpg_ctx.h"
 
 namespace {
 
@@ -533,28 +532,6 @@ __global__ __launch_bounds__(kT) void map_lists_kernel(DS d, int64_t* counts /*[
         for (int l = 0; l < 4; ++l) counts[4 * v + l] = run[l];
 }
 
-template <typename T>
-struct Buf {
-    T* p = nullptr;
-    size_t cap = 0;
-    int reserve(size_t n) {
-        if (n <= cap) return 0;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return -1;
-        cap = n;
-        return 0;
-    }
-    ~Buf() { if (p) (void)hipFree(p); }
-};
-
-double now_ms() {
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (double)ts.tv_sec * 1e3 + (double)ts.tv_nsec * 1e-6;
-}
-
 // math_utils::AngleMod<float> (math_utils.h:13-16)
 float angle_mod_f(float a) {
     double ad = (double)a;
@@ -592,18 +569,18 @@ struct dpg_dpg {
     bool win_valid = false;
     int32_t slot_node[15];
     float slot_pose[15][3];
-    Buf<int64_t> d_off;
-    Buf<float2> d_plaser;
-    Buf<float> d_range;
-    Buf<uint8_t> d_label, d_sector;
-    Buf<float4> d_geom, d_frame;
-    Buf<uint32_t> d_sect, d_active, d_grid, d_bins;
-    Buf<int32_t> d_first, d_stage, d_cand_cnt, d_acc, d_inrange, d_commit;
-    Buf<uint8_t> d_added;
-    Buf<uint16_t> d_rmask;
-    Buf<float2> d_removed, d_map_out;
-    Buf<Ctl> d_ctl;
-    Buf<int64_t> d_counts, d_base;
+    DevBuf<int64_t> d_off;
+    DevBuf<float2> d_plaser;
+    DevBuf<float> d_range;
+    DevBuf<uint8_t> d_label, d_sector;
+    DevBuf<float4> d_geom, d_frame;
+    DevBuf<uint32_t> d_sect, d_active, d_grid, d_bins;
+    DevBuf<int32_t> d_first, d_stage, d_cand_cnt, d_acc, d_inrange, d_commit;
+    DevBuf<uint8_t> d_added;
+    DevBuf<uint16_t> d_rmask;
+    DevBuf<float2> d_removed, d_map_out;
+    DevBuf<Ctl> d_ctl;
+    DevBuf<int64_t> d_counts, d_base;
     Ctl* h_ctl = nullptr;             // pinned
     hipEvent_t ev[2] = {};
 };
@@ -702,8 +679,8 @@ dpg_dpg* dpg_dpg_create(dpg_ctx* ctx, int64_t V, const int64_t* off, const float
     }
     dpg_dpg* d = new dpg_dpg();
     d->ctx = ctx;
-    d->s = reinterpret_cast<hipStream_t>(dpg_ctx_stream_of(ctx));
-    d->device = dpg_ctx_device_of(ctx);
+    d->s = ctx->stream;
+    d->device = ctx->device;
     d->p = *p;
     d->V = V;
     d->B = off[V];

@@ -1,0 +1,255 @@
+// dpg_ctx.h -- the context of the C-ABI layer, private to the HIP translation units (C++ only;
+// dpg_internal.h stays the C-compatible header of the kernels and launchers).  The extern "C"
+// boundary is split by subsystem over dpg_ctx.hip (context forms, options), dpg_icp_api.hip (scan
+// store, batched and single ICP, covariance), dpg_gn_api.hip (pose graph, marginals) and
+// dpg_sweep.hip (re-linearisation sweep, dpg_add_node); the few functions they call across each
+// other are declared at the end.  Nothing here is exported from the library.
+#ifndef DPG_CTX_H
+#define DPG_CTX_H
+
+#include <hip/hip_runtime.h>
+#include <rccl/rccl.h>
+#include <time.h>
+
+#include <algorithm>
+#include <atomic>
+#include <condition_variable>
+#include <deque>
+#include <memory>
+#include <mutex>
+#include <thread>
+#include <unordered_map>
+#include <utility>
+#include <vector>
+
+#include "../../include/dpg_slam_c.h"
+#include "dpg_chol.h"
+#include "dpg_gn_pipe.h"
+#include "dpg_internal.h"
+
+#pragma GCC visibility push(hidden)
+
+// the thread's message for dpg_last_error; returns code
+int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+
+#define HIP_TRY(expr)                                                                        \
+    do {                                                                                     \
+        hipError_t _e = (expr);                                                              \
+        if (_e != hipSuccess) return fail(DPG_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e)); \
+    } while (0)
+
+inline double now_ms() {
+    struct timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return (double)ts.tv_sec * 1e3 + (double)ts.tv_nsec * 1e-6;
+}
+
+// *p, or what the ABI's `def` fills in when the caller passed NULL
+template <typename T>
+T or_default(const T* p, void (*def)(T*)) {
+    T v;
+    if (p) v = *p;
+    else def(&v);
+    return v;
+}
+
+// A device array that owns its memory: freed when its owner goes, with the owner's device current.
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        std::swap(p, o.p);
+        std::swap(cap, o.cap);
+        return *this;
+    }
+    ~DevBuf() { release(); }
+    int reserve(size_t n) {
+        if (n <= cap) return 0;
+        release();
+        if (hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return -1;
+        cap = n;
+        return 0;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    // grow to n elements keeping the first `keep` (stream-ordered copy, synchronised)
+    int grow(size_t n, size_t keep, hipStream_t s) {
+        if (n <= cap) return 0;
+        const size_t nc = std::max(n, cap + cap / 2);
+        T* q = nullptr;
+        if (hipMalloc(reinterpret_cast<void**>(&q), nc * sizeof(T)) != hipSuccess) return -1;
+        if (p && keep && (hipMemcpyAsync(q, p, std::min(keep, cap) * sizeof(T), hipMemcpyDeviceToDevice, s) != hipSuccess ||
+                          hipStreamSynchronize(s) != hipSuccess)) {
+            (void)hipFree(q);
+            return -1;
+        }
+        if (p) (void)hipFree(p);
+        p = q;
+        cap = nc;
+        return 0;
+    }
+};
+
+struct dpg_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    hipEvent_t ev[8] = {};
+    // the batch covariance runs on `aux` beside what follows the ICP on `stream` (the pose graph
+    // does not read it): ev[2] marks its end, cov_pending until `stream` has been made to wait
+    hipStream_t aux = nullptr;
+    bool cov_pending = false, cov_on_aux = false;
+    int32_t icp_variant = DPG_ICP_ANGULAR;
+    int32_t defer_cap = 256;        // angular ICP: cooperative-queue threshold (dpg_ctx_set_icp_defer_cap)
+    int32_t cov_wg = 256;           // covariance kernel workgroups beside the pose graph (dpg_ctx_set_cov_workgroups)
+    int32_t kernel_variant = 0;     // angular ICP kernel form (dpg_ctx_set_icp_kernel_variant, A/B)
+    float map_ms = 0.f;             // last dpg_get_map kernel (HIP events map_ev)
+    hipEvent_t map_ev[2] = {};
+    // scan store (batch form)
+    DevBuf<float> full, ds;
+    DevBuf<int64_t> ds_off_dev;
+    DevBuf<int64_t> full_off_dev;  // the full clouds' offsets (the upload's device-side downsampling)
+    DevBuf<float> tree_pts;        // per-node index over the downsampled clouds (k-d tree or angle order)
+    DevBuf<uint16_t> tree_idx;
+    DevBuf<uint16_t> buckets;      // angle variant: [V][B+1] bucket starts
+    DevBuf<unsigned char> icp_scratch;   // angle variant, clouds above 4096 points: record slices
+    std::vector<int64_t> full_off, ds_off;
+    int64_t n_nodes = 0;
+    int64_t idx_valid = 0;         // angular variant: nodes [0, idx_valid) of the store have their index
+    int32_t ratio = 1;
+    int32_t max_ds = 0;
+    // staged edge batch
+    std::vector<dpg_icp_edge> h_edges;
+    DevBuf<dpg_icp_edge> edges;
+    DevBuf<dpg_icp_result> res;
+    DevBuf<double> hess;
+    DevBuf<int32_t> trace;
+    int64_t n_edges = 0;
+    int32_t max_src = 0, max_tgt = 0;
+    int32_t trace_iters = 0;
+    dpg_icp_kparams kp{};
+    bool have_cov = false;
+    // single-call scratch (dpg_run_icp / icp_cov_calculate)
+    DevBuf<float> s_pts;
+    DevBuf<dpg_icp_edge> s_edge;
+    DevBuf<dpg_icp_result> s_res;
+    DevBuf<double> s_hess;
+    DevBuf<int64_t> s_off;
+    DevBuf<float> s_tree_pts;
+    DevBuf<uint16_t> s_tree_idx;
+    DevBuf<uint16_t> s_buckets;
+    // pose graph
+    dpg_gn_dev gn{};
+    bool gn_ready = false;
+    dpg_gn_params gp{};
+    float asm_ms = 0.f, solve_ms = 0.f;
+    // node pairs (lo << 32 | hi, sorted) that share a factor of the graph set up: built from the
+    // device's factor list by the first dpg_gn_marginal_pairs after a setup
+    std::vector<uint64_t> gn_pairs;
+    bool gn_pairs_valid = false;
+    // the pipelined GN loop (dpg_gn_pipe.h): control block, two host-mapped report slots + events
+    dpg_gn_ctl* pipe_ctl = nullptr;
+    dpg_gn_slot* pipe_slot = nullptr;
+    uint32_t pipe_loop = 0;            // loops run on this device (tags their reports)
+    // multi-device forms (dpg_ctx_create_multi / _rank / _virtual): this context drives local
+    // device 0 and holds the batch as the caller sees it; `peers` are full single-device contexts
+    // of the other local devices.  Local device k is global rank rank0 + k of `world`.
+    std::vector<dpg_ctx*> peers;
+    // incremental graphs and DPG stores created on this context: dpg_ctx_destroy destroys them
+    // first (their buffers, helper thread and events all use the context's stream)
+    std::vector<std::pair<void*, void (*)(void*)>> children;
+    std::vector<ncclComm_t> comms;   // RCCL: one communicator per local device
+    dpg_coll_ops host_ops{};         // kCollHost: the caller's host-memory collectives
+    std::vector<double> host_hb;     // kCollHost: the packed system in host memory
+    struct HostColl;                 // kCollHost, pipelined GN: the collective thread (below)
+    std::unique_ptr<HostColl> hc;
+    int32_t coll = 0;                // kCollNone | kCollRccl | kCollVirtual | kCollHost
+    int32_t world = 1, rank0 = 0;
+    int32_t rank = 0;                // global rank of THIS device context (peers too)
+    // the staged batch, every form: the edges in the caller's order and their assignment --
+    // batch_owner[e] = global rank aligning edge e; shard[k] = the caller indices aligned on local
+    // device k, ascending (local result j of device k is edge shard[k][j])
+    std::vector<dpg_icp_edge> batch;
+    std::vector<int32_t> batch_owner;
+    std::vector<std::vector<int64_t>> shard;
+    bool batch_measured = false;     // assignment + dispatch order from measured costs
+    int32_t batch_runs = 0;          // runs of the staged batch so far
+    int32_t schedule = DPG_ICP_SCHEDULE_MEASURED;
+    // measured alignment cost (iterations x (source + target points)) by (target, source) pair,
+    // from earlier runs: the LPT assignment over ranks and the longest-first dispatch order
+    std::unordered_map<uint64_t, float> cost;
+    DevBuf<int32_t> shard_idx;       // per device context: its shard's caller indices
+    DevBuf<float> cost_dev;          // rank form: the all-reduced cost vector of a batch
+    dpg_chol_opts copts;             // solver options (dpg_ctx_set_solver_options)
+};
+
+// The rank form over the caller's collectives (kCollHost) in the pipelined Gauss-Newton loop: the
+// packed system's all-reduce of iteration i runs on this thread, so the host can queue iteration
+// i + 1 before iteration i's report, as over RCCL.  Per iteration, on the context stream: the
+// assembly's partial system -> pinned host buffer, an event; then a one-lane kernel that waits
+// until the thread has stored the iteration's tag in a host-mapped word (system-scope loads); then
+// the summed system -> hb_own.  The thread waits for the event, calls the caller's all-reduce in
+// place and stores the tag.  Stream order serializes the buffer's uses (the next copy into it
+// follows this iteration's copy out of it).  A failed collective still stores the tag (the stream
+// moves on) and sets `failed`, which the loop checks at every report.
+// Owns its thread, pinned buffers and events (dpg_gn_api.hip): create() hands out a complete
+// object or an error; the destructor stops and joins the thread (its queue is empty once the
+// context's stream has drained), then frees, with the context's device current.
+struct dpg_ctx::HostColl {
+    double* buf = nullptr;           // pinned: the packed system, summed in place
+    size_t cap = 0;                  // doubles
+    uint32_t* flag = nullptr;        // host-mapped: the last tag the thread completed
+    uint32_t* timed_out = nullptr;   // host-mapped: the wait kernel gave up (no tag in 120 s)
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    uint32_t next_tag = 0;
+    std::thread th;
+    std::mutex mu;
+    std::condition_variable cv;
+    std::deque<std::pair<uint32_t, hipEvent_t>> jobs;
+    size_t count = 0;                // doubles of the current system
+    uint64_t posted = 0, done = 0;
+    bool stop = false;
+    std::atomic<int> failed{0};
+    static int create(const dpg_ctx* c, std::unique_ptr<HostColl>& out);
+    ~HostColl();
+};
+
+enum { kCollNone = 0, kCollRccl = 1, kCollVirtual = 2, kCollHost = 3, kMaxVirtual = 16 };
+inline int n_dev(const dpg_ctx* c) { return 1 + (int)c->peers.size(); }
+// one process per GPU with more than one rank (dpg_ctx_create_rank / _rank_ops): the batch's
+// results and costs travel between processes
+inline bool is_rank_form(const dpg_ctx* c) {
+    return (c->coll == kCollRccl || c->coll == kCollHost) && c->peers.empty() && c->world > 1;
+}
+inline dpg_ctx* dev_ctx(dpg_ctx* c, int k) { return k == 0 ? c : c->peers[(size_t)k - 1]; }
+// made by dpg_ctx_create_multi / _rank / _virtual (even for one GPU: its calls then take the
+// sharded paths, the all-reduce included, with one rank)
+inline bool is_multi(const dpg_ctx* c) { return c->coll != kCollNone; }
+// order `stream` after the last batch covariance (before anything rewrites its inputs or reads it)
+inline int join_cov(dpg_ctx* c) {
+    if (!c->cov_pending) return DPG_OK;
+    c->cov_pending = false;
+    return hipStreamWaitEvent(c->stream, c->ev[2], 0) == hipSuccess ? DPG_OK : DPG_ERR_HIP;
+}
+
+// ---- across the layer's files ----
+extern dpg_ctx* g_default_ctx;   // icp_cov_calculate / icp_cov_sandwich without a context (dpg_ctx.hip)
+// dpg_icp_api.hip: the scan store back to its first V nodes; the staged batch building only the
+// indexes of nodes [tree_from, n_nodes); its results in the caller's order (learn: into the cost memory)
+void scans_truncate(dpg_ctx* c, int64_t V);
+int icp_batch_run_from(dpg_ctx* c, int64_t tree_from);
+int batch_fetch(dpg_ctx* c, dpg_icp_result* results, double* hess, bool learn);
+// dpg_gn_api.hip: the Gauss-Newton loop on a set-up graph whose poses are set
+int gn_loop(dpg_ctx* c, const dpg_gn_params& P, double* poses, double t0, double t1, dpg_gn_stats* st);
+
+#pragma GCC visibility pop
+
+#endif

@@ -22,15 +22,12 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
-#include <time.h>
 
 #include <algorithm>
 #include <future>
 #include <vector>
 
-#include "dpg_chol.h"
-#include "dpg_internal.h"
-#include "dpg_gn_pipe.h"
+#include "dpg_ctx.h"
 
 namespace {
 
@@ -466,17 +463,11 @@ extern "C" void dpg_gn_dev_free(dpg_gn_dev* g) {
     memset(g, 0, sizeof(*g));
 }
 
-static double gn_wall_ms() {
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (double)ts.tv_sec * 1e3 + (double)ts.tv_nsec * 1e-6;
-}
-
 extern "C" int dpg_gn_dev_alloc(dpg_gn_dev* g, int64_t n, const dpg_factor* F, int64_t nf,
                                 int64_t shard_begin, int64_t shard_end, const dpg_chol_opts* opts, void* sync_stream) {
     memset(g, 0, sizeof(*g));
     if (n <= 0 || nf < 0 || n > (int64_t)1 << 28) return DPG_ERR_ARG;
-    const double t0 = gn_wall_ms();
+    const double t0 = now_ms();
     // unique pairs (lo, hi) of Between factors, as sorted 64-bit keys lo << 32 | hi; every
     // factor's pair index found once
     std::vector<uint64_t> fkey((size_t)nf, ~0ull);
@@ -506,14 +497,14 @@ extern "C" int dpg_gn_dev_alloc(dpg_gn_dev* g, int64_t n, const dpg_factor* F, i
     const dpg_chol_opts copt = opts ? *opts : dpg_chol_opts{};
     double sym_ms = 0.0;
     std::future<void*> sym_job = std::async(std::launch::async, [&]() -> void* {
-        const double ts = gn_wall_ms();
+        const double ts = now_ms();
         void* ch = nullptr;
         dpg_chol_opts o = copt;
         dpg_chol_sym S;
         if (dpg_chol_symbolic(n, plo.data(), phi.data(), P, &o, &S) ||
             dpg_chol_create_sym_plan(&ch, n, plo.data(), phi.data(), P, &S, &o))
             ch = nullptr;   // the PCG solver still works; dpg_gn_dev_solve reports which ran
-        sym_ms = gn_wall_ms() - ts;
+        sym_ms = now_ms() - ts;
         return ch;
     });
     std::vector<int32_t> fpair((size_t)nf, -1);
@@ -565,9 +556,9 @@ extern "C" int dpg_gn_dev_alloc(dpg_gn_dev* g, int64_t n, const dpg_factor* F, i
             srcup[(size_t)at[(size_t)lo]++] = (int32_t)(n + p);
         }
     }
-    const double t1 = gn_wall_ms();
+    const double t1 = now_ms();
     void* chol = sym_job.get();
-    const double t2 = gn_wall_ms();
+    const double t2 = now_ms();
     if (sync_stream && hipStreamSynchronize(reinterpret_cast<hipStream_t>(sync_stream)) != hipSuccess) {
         if (chol) dpg_chol_destroy(chol);
         return DPG_ERR_HIP;
@@ -612,7 +603,7 @@ extern "C" int dpg_gn_dev_alloc(dpg_gn_dev* g, int64_t n, const dpg_factor* F, i
     g->chol = chol;
     if (g->chol && dpg_chol_create_sym_upload(&g->chol)) g->chol = nullptr;   // (destroyed on error)
     if (g->chol) dpg_chol_keep_inverse(g->chol, 1);   // chord steps reuse the factor: L11^-1 for their solves
-    const double t3 = gn_wall_ms();
+    const double t3 = now_ms();
     double bt[2] = {0.0, 0.0};
     if (g->chol) dpg_chol_build_times(g->chol, bt);
     g->setup_ms[0] = t1 - t0;                             // (beside the next two from the pairs on)
@@ -786,7 +777,7 @@ __device__ __forceinline__ void clear_sync(int32_t* sync, int64_t n_words, int32
 }
 
 // a report into host memory: the fields, then the tag the host polls.  The slot is fine-grained
-// (coherent, uncached) host memory (dpg_api.hip ensure_pipe): the fields go out as system-scope
+// (coherent, uncached) host memory (dpg_gn_api.hip ensure_pipe): the fields go out as system-scope
 // stores, and the tag only after all of them have been acknowledged (s_waitcnt vmcnt(0)), so the
 // host never sees the tag before the fields -- without __threadfence_system's write-back of the
 // whole L2, which holds nothing of the slot's
@@ -830,7 +821,7 @@ __global__ void pipe_init_kernel(dpg_gn_ctl* ctl, int32_t reuse, int32_t last_wa
 }
 
 // the end of one iteration: the error (chi2_kernel's sum, same order), its report, then the next
-// iteration decided exactly as the host loop does (dpg_api.hip gn_loop: the stop rule;
+// iteration decided exactly as the host loop does (dpg_gn_api.hip gn_loop: the stop rule;
 // dpg_gn_dev_solve_async: the chord rule), and the solver's counters cleared for it
 // chi2_sum != NULL (multi-device forms): the error is the all-reduced sum already in hb, not this
 // device's per-node terms.  vote != NULL (world > 1): max |delta| and the status are taken from the
@@ -1024,7 +1015,7 @@ static int pcg_solve(dpg_gn_dev* g, const double* hb, const dpg_gn_params* gp, h
     return it;
 }
 
-// the rank form's host collective (dpg_api.hip, dpg_ctx::HostColl): the stream waits here until the
+// the rank form's host collective (dpg_gn_api.hip, dpg_ctx::HostColl): the stream waits here until the
 // collective thread has stored this iteration's tag.  One lane; vector loads at system scope (the
 // word is host memory), s_sleep between polls, a 120 s bound on the 100 MHz clock.
 __global__ void host_wait_kernel(const uint32_t* flag, uint32_t tag, uint32_t* timed_out) {

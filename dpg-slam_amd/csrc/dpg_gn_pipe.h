@@ -8,7 +8,7 @@
 // later, and every launch of an iteration checks the gate first (a gated-off launch exits at
 // once).  The host keeps one iteration queued ahead of the one it reads, so the queue never
 // drains; an iteration enqueued after the last one is all no-ops.  The arithmetic and the
-// decisions are the host loop's (dpg_api.hip gn_loop), so poses, errors and iteration counts
+// decisions are the host loop's (dpg_gn_api.hip gn_loop), so poses, errors and iteration counts
 // are identical.
 #ifndef DPG_GN_PIPE_H
 #define DPG_GN_PIPE_H

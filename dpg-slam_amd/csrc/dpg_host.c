@@ -241,3 +241,51 @@ void dpg_relative_from_blocks(const int32_t* pairs, int64_t n, const double* X, 
         else dpg_relative_covariance(X + 3 * i, X + 3 * j, B, B + 9, B + 18, out + 9 * q);
     }
 }
+
+static void sym6(double* m, int i, int j, double v) { m[6 * i + j] = v; m[6 * j + i] = v; }
+static void swap_d(double* a, double* b) { const double t = *a; *a = *b; *b = t; }
+
+/* d2J_dX2 and d2J_dZdX cov_z d2J_dZdX^T from the 16 sums of cov6_kernel (+ the pair counts), then
+ * cov6 = 0.01 inv(H) M inv(H) (Gauss-Jordan with partial pivoting, fp64, fixed order) */
+int dpg_cov6_from_sums(const double* sm, int64_t nh, int64_t nb, double cov6[36]) {
+    double H[36] = {0}, M[36] = {0};
+    enum { X = 0, Y = 1, Z = 2, A = 3, B = 4, C = 5 };
+    sym6(H, X, X, 2.0 * (double)nh); sym6(H, Y, Y, 2.0 * (double)nh); sym6(H, Z, Z, 2.0 * (double)nh);
+    sym6(H, X, A, sm[0]); sym6(H, Y, A, sm[1]); sym6(H, A, A, sm[2]); sym6(H, Z, B, sm[3]); sym6(H, Z, C, sm[4]);
+    sym6(H, B, B, sm[5]); sym6(H, B, C, sm[6]); sym6(H, C, C, sm[7]);
+    sym6(M, X, X, 8.0 * (double)nb); sym6(M, Y, Y, 8.0 * (double)nb); sym6(M, Z, Z, 8.0 * (double)nb);
+    sym6(M, X, A, sm[8]); sym6(M, Y, A, sm[9]); sym6(M, A, A, sm[10]); sym6(M, Z, B, sm[11]); sym6(M, Z, C, sm[12]);
+    sym6(M, B, B, sm[13]); sym6(M, B, C, sm[14]); sym6(M, C, C, sm[15]);
+    double I[36] = {0};
+    for (int i = 0; i < 6; ++i) I[7 * i] = 1.0;
+    for (int c = 0; c < 6; ++c) {
+        int p = c;
+        for (int r = c + 1; r < 6; ++r)
+            if (fabs(H[6 * r + c]) > fabs(H[6 * p + c])) p = r;
+        if (!(fabs(H[6 * p + c]) > 0.0)) return DPG_ERR_NUMERIC;
+        if (p != c)
+            for (int k = 0; k < 6; ++k) { swap_d(&H[6 * p + k], &H[6 * c + k]); swap_d(&I[6 * p + k], &I[6 * c + k]); }
+        const double d = H[6 * c + c];
+        for (int k = 0; k < 6; ++k) { H[6 * c + k] /= d; I[6 * c + k] /= d; }
+        for (int r = 0; r < 6; ++r) {
+            if (r == c) continue;
+            const double f = H[6 * r + c];
+            if (f == 0.0) continue;
+            for (int k = 0; k < 6; ++k) { H[6 * r + k] -= f * H[6 * c + k]; I[6 * r + k] -= f * I[6 * c + k]; }
+        }
+    }
+    double T1[36];
+    for (int i = 0; i < 6; ++i)
+        for (int j = 0; j < 6; ++j) {
+            double acc = 0.0;
+            for (int k = 0; k < 6; ++k) acc += I[6 * i + k] * M[6 * k + j];
+            T1[6 * i + j] = acc;
+        }
+    for (int i = 0; i < 6; ++i)
+        for (int j = 0; j < 6; ++j) {
+            double acc = 0.0;
+            for (int k = 0; k < 6; ++k) acc += T1[6 * i + k] * I[6 * k + j];
+            cov6[6 * i + j] = 0.01 * acc;
+        }
+    return DPG_OK;
+}

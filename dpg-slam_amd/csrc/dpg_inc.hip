@@ -30,7 +30,6 @@
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
-#include <time.h>
 
 #include <algorithm>
 #include <atomic>
@@ -43,18 +42,11 @@
 #include <unordered_map>
 #include <vector>
 
-#include "dpg_chol.h"
-#include "dpg_internal.h"
+#include "dpg_ctx.h"
 
 namespace {
 
 constexpr int kThreads = 256;
-
-double now_ms() {
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (double)ts.tv_sec * 1e3 + (double)ts.tv_nsec * 1e-6;
-}
 
 template <typename T>
 int dgrow(T** d, size_t* cap, size_t n, hipStream_t s, size_t keep) {
@@ -367,7 +359,7 @@ dpg_inc* dpg_inc_create(dpg_ctx* ctx, const dpg_inc_params* p) {
         set_err(DPG_ERR_ARG, "dpg_inc_create: ctx is NULL");
         return nullptr;
     }
-    if (dpg_ctx_num_gpus(ctx) != 1 || dpg_ctx_is_multi(ctx)) {
+    if (n_dev(ctx) != 1 || is_multi(ctx)) {
         set_err(DPG_ERR_ARG, "dpg_inc_create: the incremental graph needs a single-device context (dpg_ctx_create)");
         return nullptr;
     }
@@ -378,7 +370,7 @@ dpg_inc* dpg_inc_create(dpg_ctx* ctx, const dpg_inc_params* p) {
     if (q->P.relinearize_skip < 1) q->P.relinearize_skip = 1;
     if (q->P.reorder_every < 1) q->P.reorder_every = 1;
     if (q->P.reorder_lead < 0 || q->P.reorder_lead >= q->P.reorder_every) q->P.reorder_lead = 0;
-    q->opts = *dpg_ctx_chol_opts(ctx);   // the context's solver options
+    q->opts = ctx->copts;   // the context's solver options
     q->P.gn.linear_solver = DPG_SOLVER_CHOLESKY;
     dpg_ctx_adopt(ctx, q, [](void* x) { dpg_inc_destroy(static_cast<dpg_inc*>(x)); });
     return q;
@@ -426,7 +418,7 @@ int dpg_inc_abort_prepare(dpg_inc* q) {
 void dpg_inc_destroy(dpg_inc* q) {
     if (!q) return;
     dpg_ctx_release_child(q->ctx, q);
-    hipStream_t s = reinterpret_cast<hipStream_t>(dpg_ctx_stream_of(q->ctx));
+    hipStream_t s = q->ctx->stream;
     (void)hipStreamSynchronize(s);
     void* ptrs[] = {q->g.factors, q->g.up_cptr, q->g.up_clist, q->g.hb_own, q->g.partials, q->g.scal3,
                     q->theta, q->est, q->maxd, q->cnt, q->est_nxt, q->maxd_nxt, q->theta_bak, q->est_bak};
@@ -606,8 +598,8 @@ int dpg_inc_update(dpg_inc* q, int64_t n_new, const double* init, const dpg_fact
     if (!q || n_new < 0 || n_factors < 0 || (n_new > 0 && !init) || (n_factors > 0 && !factors))
         return set_err(DPG_ERR_ARG, "dpg_inc_update: bad arguments");
     const double t0 = now_ms();
-    hipStream_t s = reinterpret_cast<hipStream_t>(dpg_ctx_stream_of(q->ctx));
-    if (hipSetDevice(dpg_ctx_device_of(q->ctx)) != hipSuccess) return set_err(DPG_ERR_HIP, "hipSetDevice failed");
+    hipStream_t s = q->ctx->stream;
+    if (hipSetDevice(q->ctx->device) != hipSuccess) return set_err(DPG_ERR_HIP, "hipSetDevice failed");
     const int64_t V0 = q->V, V1 = V0 + n_new;
     // validate before touching any state
     for (int64_t k = 0; k < n_factors; ++k) {
@@ -860,8 +852,8 @@ int dpg_inc_save(dpg_inc* q, const char* path) {
     if (h.n_scans < h.V) h.n_scans = 0;
     const size_t V = (size_t)h.V;
     std::vector<double> theta(3 * V), est(3 * V), maxd(V);
-    hipStream_t s = reinterpret_cast<hipStream_t>(dpg_ctx_stream_of(q->ctx));
-    if (hipSetDevice(dpg_ctx_device_of(q->ctx)) != hipSuccess) return set_err(DPG_ERR_HIP, "hipSetDevice failed");
+    hipStream_t s = q->ctx->stream;
+    if (hipSetDevice(q->ctx->device) != hipSuccess) return set_err(DPG_ERR_HIP, "hipSetDevice failed");
     if (V && (hipMemcpyAsync(theta.data(), q->theta, sizeof(double) * 3 * V, hipMemcpyDeviceToHost, s) != hipSuccess ||
               hipMemcpyAsync(est.data(), q->est, sizeof(double) * 3 * V, hipMemcpyDeviceToHost, s) != hipSuccess ||
               hipMemcpyAsync(maxd.data(), q->maxd, sizeof(double) * V, hipMemcpyDeviceToHost, s) != hipSuccess))
@@ -903,9 +895,9 @@ int64_t dpg_inc_export(dpg_inc* q, int64_t* updates, dpg_factor* F, int32_t* cre
     if (F && k) memcpy(F, q->F.data(), sizeof(dpg_factor) * k);
     if (created && k) memcpy(created, q->f_created.data(), sizeof(int32_t) * k);
     const size_t V = (size_t)q->V;
-    hipStream_t s = reinterpret_cast<hipStream_t>(dpg_ctx_stream_of(q->ctx));
+    hipStream_t s = q->ctx->stream;
     if (V && (theta || est || maxd)) {
-        if (hipSetDevice(dpg_ctx_device_of(q->ctx)) != hipSuccess) return set_err(DPG_ERR_HIP, "hipSetDevice failed");
+        if (hipSetDevice(q->ctx->device) != hipSuccess) return set_err(DPG_ERR_HIP, "hipSetDevice failed");
         if ((theta && hipMemcpyAsync(theta, q->theta, sizeof(double) * 3 * V, hipMemcpyDeviceToHost, s) != hipSuccess) ||
             (est && hipMemcpyAsync(est, q->est, sizeof(double) * 3 * V, hipMemcpyDeviceToHost, s) != hipSuccess) ||
             (maxd && hipMemcpyAsync(maxd, q->maxd, sizeof(double) * V, hipMemcpyDeviceToHost, s) != hipSuccess) ||
@@ -1017,8 +1009,8 @@ dpg_inc* dpg_inc_load(dpg_ctx* ctx, const char* path) {
     q->F = F;
     q->n_dev_f = 0;
     q->f_created = created;
-    hipStream_t s = reinterpret_cast<hipStream_t>(dpg_ctx_stream_of(ctx));
-    if (hipSetDevice(dpg_ctx_device_of(ctx)) != hipSuccess) return bail(DPG_ERR_HIP, "hipSetDevice failed");
+    hipStream_t s = ctx->stream;
+    if (hipSetDevice(ctx->device) != hipSuccess) return bail(DPG_ERR_HIP, "hipSetDevice failed");
     int rc = 0;
     rc |= dgrow(&q->theta, &q->c_theta, 3 * V, s, 0);
     rc |= dgrow(&q->est, &q->c_est, 3 * V, s, 0);
@@ -1037,7 +1029,7 @@ dpg_inc* dpg_inc_load(dpg_ctx* ctx, const char* path) {
 int dpg_inc_get_poses(dpg_inc* q, double* poses, int64_t n) {
     if (!q || !poses || n < 0 || n > q->V) return set_err(DPG_ERR_ARG, "dpg_inc_get_poses: bad arguments");
     if (n == 0) return DPG_OK;
-    hipStream_t s = reinterpret_cast<hipStream_t>(dpg_ctx_stream_of(q->ctx));
+    hipStream_t s = q->ctx->stream;
     if (hipMemcpyAsync(poses, q->est, sizeof(double) * 3 * (size_t)n, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)
         return set_err(DPG_ERR_HIP, "dpg_inc_get_poses: copy failed");
@@ -1047,52 +1039,50 @@ int dpg_inc_get_poses(dpg_inc* q, double* poses, int64_t n) {
 // ISAM2::marginalCovariance: the selected inverse of the factor the last update left (read only:
 // L, the tracked factorization and the pending forward-solve state are not touched, so the next
 // update's partial re-elimination continues from the same values)
-int dpg_inc_marginals(dpg_inc* q, const int32_t* nodes, int64_t n, double* cov_out) {
+// the graph holds a factor to read (host only; every marginals entry point)
+static int inc_marginals_state(dpg_inc* q, const char* fn) {
     if (!q || !q->g.chol || q->V == 0 || q->updates == 0)
-        return set_err(DPG_ERR_STATE, "dpg_inc_marginals: the graph holds no factorization yet");
-    if (dpg_ctx_is_multi(q->ctx)) return set_err(DPG_ERR_STATE, "dpg_inc_marginals: marginals are single-device");
+        return fail(DPG_ERR_STATE, "%s: the graph holds no factorization yet", fn);
+    if (is_multi(q->ctx)) return fail(DPG_ERR_STATE, "%s: marginals are single-device", fn);
     if (q->prepared)
-        return set_err(DPG_ERR_STATE, "dpg_inc_marginals: an update is prepared (its analysis has replaced the factor's)");
-    if (!cov_out || n < 0 || (!nodes && n != q->V)) return set_err(DPG_ERR_ARG, "dpg_inc_marginals: bad arguments");
-    if (dpg_chol_selinv_check(q->g.chol, nodes, n, nullptr, 0))
-        return set_err(DPG_ERR_ARG, "dpg_inc_marginals: a node is out of range");
-    if (hipSetDevice(dpg_ctx_device_of(q->ctx)) != hipSuccess) return set_err(DPG_ERR_HIP, "hipSetDevice failed");
-    const int rc = dpg_chol_marginals(q->g.chol, nodes, n, nullptr, 0, cov_out, dpg_ctx_stream_of(q->ctx));
-    if (rc == DPG_ERR_STATE) return set_err(rc, "dpg_inc_marginals: the graph holds no factorization (failed or restored update)");
-    if (rc == DPG_ERR_NUMERIC) return set_err(rc, "dpg_inc_marginals: H is not positive definite");
-    if (rc) return set_err(rc, "dpg_inc_marginals: selected inversion failed");
+        return fail(DPG_ERR_STATE, "%s: an update is prepared (its analysis has replaced the factor's)", fn);
+    return DPG_OK;
+}
+
+int dpg_inc_marginals(dpg_inc* q, const int32_t* nodes, int64_t n, double* cov_out) {
+    const char* fn = "dpg_inc_marginals";
+    int rc = inc_marginals_state(q, fn);
+    if (rc) return rc;
+    if (!cov_out || n < 0 || (!nodes && n != q->V)) return fail(DPG_ERR_ARG, "%s: bad arguments", fn);
+    if (dpg_chol_selinv_check(q->g.chol, nodes, n, nullptr, 0)) return fail(DPG_ERR_ARG, "%s: a node is out of range", fn);
+    if (hipSetDevice(q->ctx->device) != hipSuccess) return set_err(DPG_ERR_HIP, "hipSetDevice failed");
+    rc = dpg_chol_marginals(q->g.chol, nodes, n, nullptr, 0, cov_out, q->ctx->stream);
+    if (rc == DPG_ERR_STATE) return fail(rc, "%s: the graph holds no factorization (failed or restored update)", fn);
+    if (rc == DPG_ERR_NUMERIC) return fail(rc, "%s: H is not positive definite", fn);
+    if (rc) return fail(rc, "%s: selected inversion failed", fn);
     return DPG_OK;
 }
 
 // Marginals::jointMarginalCovariance on the incremental graph: blocks of Sigma for any nodes from
 // root paths of the factor the last update left (dpg_chol_joint; read only, as above)
-static int inc_joint_err(const char* fn, int rc, const char* what) {
-    char msg[200];
-    snprintf(msg, sizeof msg, "%s: %s", fn, what);
-    return set_err(rc, msg);
-}
-
 // host only: the graph holds a factor to read and the request is well formed
 static int inc_joint_check(dpg_inc* q, const char* fn, int by_nodes, const int32_t* idx, int64_t n, const double* out) {
-    if (!q || !q->g.chol || q->V == 0 || q->updates == 0)
-        return inc_joint_err(fn, DPG_ERR_STATE, "the graph holds no factorization yet");
-    if (dpg_ctx_is_multi(q->ctx)) return inc_joint_err(fn, DPG_ERR_STATE, "marginals are single-device");
-    if (q->prepared)
-        return inc_joint_err(fn, DPG_ERR_STATE, "an update is prepared (its analysis has replaced the factor's)");
-    if (n < 0 || (n > 0 && (!idx || !out))) return inc_joint_err(fn, DPG_ERR_ARG, "bad arguments");
+    const int rc = inc_marginals_state(q, fn);
+    if (rc) return rc;
+    if (n < 0 || (n > 0 && (!idx || !out))) return fail(DPG_ERR_ARG, "%s: bad arguments", fn);
     for (int64_t k = 0, e = by_nodes ? n : 2 * n; k < e; ++k)
-        if (idx[k] < 0 || idx[k] >= q->V) return inc_joint_err(fn, DPG_ERR_ARG, "a node is out of range");
+        if (idx[k] < 0 || idx[k] >= q->V) return fail(DPG_ERR_ARG, "%s: a node is out of range", fn);
     return DPG_OK;
 }
 
 static int inc_joint_blocks(dpg_inc* q, const char* fn, int by_nodes, const int32_t* idx, int64_t n, double* out) {
     int rc = inc_joint_check(q, fn, by_nodes, idx, n, out);
     if (rc || n == 0) return rc;
-    if (hipSetDevice(dpg_ctx_device_of(q->ctx)) != hipSuccess) return set_err(DPG_ERR_HIP, "hipSetDevice failed");
-    rc = dpg_chol_joint(q->g.chol, by_nodes, idx, n, out, dpg_ctx_stream_of(q->ctx), nullptr);
-    if (rc == DPG_ERR_STATE) return inc_joint_err(fn, rc, "the graph holds no factorization (failed or restored update)");
-    if (rc == DPG_ERR_NUMERIC) return inc_joint_err(fn, rc, "H is not positive definite");
-    if (rc) return inc_joint_err(fn, rc, "the path solve failed");
+    if (hipSetDevice(q->ctx->device) != hipSuccess) return set_err(DPG_ERR_HIP, "hipSetDevice failed");
+    rc = dpg_chol_joint(q->g.chol, by_nodes, idx, n, out, q->ctx->stream, nullptr);
+    if (rc == DPG_ERR_STATE) return fail(rc, "%s: the graph holds no factorization (failed or restored update)", fn);
+    if (rc == DPG_ERR_NUMERIC) return fail(rc, "%s: H is not positive definite", fn);
+    if (rc) return fail(rc, "%s: the path solve failed", fn);
     return DPG_OK;
 }
 
@@ -1114,7 +1104,7 @@ int dpg_inc_relative_covariances(dpg_inc* q, const int32_t* pairs, int64_t n, do
     std::vector<double> blocks((size_t)(27 * n));
     if ((rc = inc_joint_blocks(q, fn, 0, tri.data(), 3 * n, blocks.data()))) return rc;
     std::vector<double> X((size_t)(3 * q->V));
-    hipStream_t s = reinterpret_cast<hipStream_t>(dpg_ctx_stream_of(q->ctx));
+    hipStream_t s = q->ctx->stream;
     if (hipMemcpyAsync(X.data(), q->theta, sizeof(double) * X.size(), hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)
         return set_err(DPG_ERR_HIP, "dpg_inc_relative_covariances: copy failed");

@@ -1,6 +1,7 @@
 /*
- * dpg_internal.h -- private structures shared by the C-ABI layer (dpg_api.hip) and the HIP
- * kernel translation units (dpg_icp.hip, dpg_gn.hip).  Not part of the public ABI.
+ * dpg_internal.h -- private structures shared by the C-ABI layer (dpg_ctx.hip, dpg_icp_api.hip,
+ * dpg_gn_api.hip, dpg_sweep.hip; their own C++ header is dpg_ctx.h) and the HIP kernel
+ * translation units (dpg_icp.hip, dpg_gn.hip).  C-compatible.  Not part of the public ABI.
  */
 #ifndef DPG_INTERNAL_H
 #define DPG_INTERNAL_H
@@ -13,20 +14,17 @@
 extern "C" {
 #endif
 
-/* error message + code for dpg_last_error; the context's stream / device (dpg_api.hip) */
+/* error message + code for dpg_last_error (dpg_ctx.hip) */
 int dpg_set_error(int code, const char* msg);
 dpg_ctx* dpg_inc_ctx(dpg_inc* g);   /* the context an incremental graph runs on (dpg_inc.hip) */
 /* the structural half of the next dpg_inc_update (host only: n_new nodes, node pairs that may carry
  * its Between factors), so that it can run while the GPU aligns the node's edges (dpg_inc.hip) */
 int dpg_inc_prepare(dpg_inc* g, int64_t n_new, const int32_t* pairs, int64_t n_pairs);
 int dpg_inc_abort_prepare(dpg_inc* g);
-int dpg_ctx_is_multi(dpg_ctx* c);
 /* the scan store as host copies, and the neighbour index of every stored node (the graph
  * checkpoint, dpg_inc_save / dpg_inc_load in dpg_inc.hip) */
 int dpg_scans_export(dpg_ctx* c, int64_t* n_nodes, int32_t* ratio, int64_t* off, float* pts);
 int dpg_scans_index_all(dpg_ctx* c);
-void* dpg_ctx_stream_of(dpg_ctx* c);
-int dpg_ctx_device_of(dpg_ctx* c);
 /* children of a context (incremental graphs, DPG stores): dpg_ctx_destroy destroys the ones still
  * alive, newest first; a child's own destroy releases it from the list */
 void dpg_ctx_adopt(dpg_ctx* c, void* child, void (*destroy)(void*));
@@ -77,6 +75,8 @@ size_t dpg_icp_lds_bytes(int32_t lds_tgt, int32_t cells_max);
 /* the 6x6 covariance sums of icp_cov_sandwich (dpg_icp.hip cov6_kernel): out[16] */
 int dpg_launch_cov6(const float* pts_dev, int32_t n_data, int32_t n_model, const float* T6_dev, double* out_dev,
                     void* stream);
+/* cov6 = 0.01 inv(H) M inv(H) from those sums and the pair counts (dpg_host.c; DPG_ERR_NUMERIC: H singular) */
+__attribute__((visibility("hidden"))) int dpg_cov6_from_sums(const double* sm, int64_t nh, int64_t nb, double cov6[36]);
 /* k-d tree variant (dpg_icp_kd.hip): per-node trees over the downsampled clouds, then ICP. */
 int dpg_launch_kdtree_build(const float* ds_pts_dev, const int64_t* ds_off_dev, int64_t n_nodes,
                             int32_t max_points, float* tree_pts_dev, uint16_t* tree_idx_dev, void* stream);
@@ -233,8 +233,6 @@ void dpg_relative_from_blocks(const int32_t* pairs, int64_t n, const double* X, 
    hipStreamSynchronize(sync_stream) when given -- the device allocations and uploads */
 int dpg_gn_dev_alloc(dpg_gn_dev* g, int64_t n_nodes, const dpg_factor* factors, int64_t n_factors,
                      int64_t shard_begin, int64_t shard_end, const struct dpg_chol_opts* opts, void* sync_stream);
-/* the context's solver options (dpg_ctx_set_solver_options) */
-const struct dpg_chol_opts* dpg_ctx_chol_opts(dpg_ctx* c);
 void dpg_gn_dev_free(dpg_gn_dev* g);
 int64_t dpg_gn_dev_hb_size(const dpg_gn_dev* g);
 int64_t dpg_gn_dev_vote_offset(const dpg_gn_dev* g);   /* first vote word of the packed buffer */

@@ -1,6 +1,6 @@
 """The CPU restatement behind DpgSLAM (dpgslam/slam.py) for the tests: the same backend methods as
 slam.GpuBackend, computed by the oracle (oracle/, test infrastructure).  Per node it restates
-dpg_add_node (dpg_api.hip; updatePoseGraphObsConstraints, dpg_slam.cc:255-314): the successive
+dpg_add_node (dpg_sweep.hip; updatePoseGraphObsConstraints, dpg_slam.cc:255-314): the successive
 pair and the loop-closure candidates (i, prev), i < V - 2, by the float distance rule, aligned one
 by one by the oracle's ICP, the factors in the same order, then OracleIncGraph.update."""
 import numpy as np

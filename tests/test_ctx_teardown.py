@@ -1,0 +1,42 @@
+"""dpg_ctx_destroy on a context whose children are still alive.  Python's Context.close closes the
+DPG stores and incremental graphs first, so the C side's own order -- children (newest first),
+peers, communicators, the drained stream, the collective thread, then the context's device arrays
+-- only runs when a C caller, or a finalizer that reached the context first, destroys the raw
+handle."""
+import numpy as np
+import pytest
+
+
+def _two_node_graph():
+    """A prior on node 0 and one exactly consistent Between: the optimum is x0 = 0, x1 = (2, 0, 0)."""
+    from dpgslam import api
+    F = np.concatenate([api.prior_factor(0, (0.0, 0.0, 0.0), (0.3, 0.3, 0.1)),
+                        api.between_factor(0, 1, (2.0, 0.0, 0.0), (0.2, 0.2, 0.1))])
+    X0 = np.array([[0.3, -0.1, 0.1], [2.2, 0.1, -0.1]])
+    X_opt = np.array([[0.0, 0.0, 0.0], [2.0, 0.0, 0.0]])
+    return X0, F, X_opt
+
+
+@pytest.mark.gpu
+def test_destroy_with_live_children_then_fresh_context():
+    from dpgslam import api
+    from graphs import pose_diff
+    X0, F, X_opt = _two_node_graph()
+    ctx = api.Context(0)
+    inc = api.IncGraph(ctx)
+    inc.update(X0, F)
+    assert inc.V == 2
+    ranges = np.full((2, 16), 5.0, np.float32)
+    geom = np.tile(np.array([-np.pi, np.pi, 8.0], np.float32), (2, 1))
+    store = api.DpgStore(ctx, ranges, geom)
+    # the raw handle goes while both children live: the context destroys them itself
+    api.lib().dpg_ctx_destroy(ctx.handle)
+    ctx.handle = None
+    for child in (inc, store):
+        child.close()   # nothing left to destroy: only the dangling handle is dropped
+        assert child.handle is None
+    ctx.close()
+    with api.Context(0) as fresh:
+        X, st = fresh.optimize_graph(X0, F)
+        # zero-residual optimum, fp64 Gauss-Newton to its default step tolerance (as smoke())
+        assert st.iterations > 0 and np.abs(pose_diff(X, X_opt)).max() < 1e-9, X

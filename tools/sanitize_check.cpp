@@ -15,6 +15,7 @@
 
 #include "../dpg-slam_amd/csrc/dpg_chol.h"
 #include "../dpg-slam_amd/csrc/dpg_chol_plan.h"
+#include "../dpg-slam_amd/csrc/dpg_internal.h"
 #include "../oracle/dpg_oracle.h"
 
 struct oracle_dpg;
@@ -189,6 +190,17 @@ int main() {
     }
     // the GPU solver's host plans of larger graphs
     REQUIRE(plan_checks() == 0);
+    // the 6x6 covariance sandwich from its 16 sums: a regular d2J_dX2 (the diagonal dominates the
+    // couplings), then a singular one (no pairs, no sums: H = 0)
+    {
+        const double sm[16] = {3.0, -2.0, 90.0, 4.0, -1.0, 70.0, 5.0, 60.0, 6.0, -4.0, 300.0, 8.0, -2.0, 200.0, 9.0, 150.0};
+        const double zero[16] = {0.0};
+        double cov6[36];
+        REQUIRE(dpg_cov6_from_sums(sm, 40, 40, cov6) == DPG_OK);
+        for (int i = 0; i < 36; ++i) REQUIRE(std::isfinite(cov6[i]));
+        REQUIRE(dpg_cov6_from_sums(zero, 0, 0, cov6) == DPG_ERR_NUMERIC);
+        printf("cov6 ok: regular and singular sums\n");
+    }
     // DPG change detection: pass 0 = the first half, pass 1 = the second half as a later pass
     dpg_change_params cp;
     memset(&cp, 0, sizeof(cp));
