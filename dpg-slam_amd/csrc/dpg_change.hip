@@ -25,6 +25,8 @@
 //   commit_kernel, apply_added_kernel, apply_removed_kernel   labels + sector of REMOVED (:714-743)
 //   deactivate_kernel     updateNodesAndSectorStatus (:888-911, dpg_node.cc:28-96): one block per
 //                         past node over the removed points
+//   occ_raster_kernel, occ_finalize_kernel, beam_geometry_kernel   the occupancy grid of the active
+//                         pose graph (dpg_occupancy_grid): raster_kernel's sampling, counted per cell
 // Every fp32 expression is evaluated as the reference writes it (-ffp-contract=off); the trig of
 // node frames is taken on the host with the same libm calls the oracle uses.  Q8 fixes: see
 // include/dpg_slam_c.h and DESIGN.md §3.
@@ -532,6 +534,146 @@ __global__ __launch_bounds__(kT) void map_lists_kernel(DS d, int64_t* counts /*[
         for (int l = 0; l < 4; ++l) counts[4 * v + l] = run[l];
 }
 
+// ---- occupancy grid of the active pose graph (dpg_occupancy_grid; semantics in dpg_slam_c.h) ----
+// The counting form of raster_kernel over every active node: the same beam x lane-group split and
+// the same float t chain, but every sample adds one to its cell's miss counter and every end point
+// one to its cell's hit counter.  A workgroup accumulates in an LDS hash table first ((cell, kind)
+// key claimed by CAS, count by an LDS add) and flushes one global atomicAdd per distinct key; an add
+// whose probe sequence finds no slot goes straight to the global counter.  All sums are integer, so
+// the result does not depend on which path or order an add took.
+struct OccCtl { unsigned long long samples, oob, hits, direct, flushed, beams, pad0, pad1; };
+
+template <int H>
+__device__ __forceinline__ void occ_add(uint32_t* keys, uint32_t* cnt, int32_t* hits, int32_t* misses, int64_t c,
+                                        bool hit, unsigned long long* direct) {
+    const uint32_t key = ((uint32_t)c << 1) | (hit ? 1u : 0u);      // c < 2^25
+    if (H > 0) {
+        constexpr int bits = __builtin_ctz((unsigned)(H > 1 ? H : 2));   // H is a power of two
+        uint32_t h = ((key * 2654435761u) >> (32 - bits)) & (uint32_t)(H - 1);   // multiplicative hash
+        for (int probe = 0; probe < 8; ++probe, h = (h + 1) & (uint32_t)(H - 1)) {
+            const uint32_t old = atomicCAS(&keys[h], kEmpty, key);
+            if (old == kEmpty || old == key) { atomicAdd(&cnt[h], 1u); return; }
+        }
+    }
+    atomicAdd((hit ? hits : misses) + c, 1);
+    ++*direct;
+}
+
+template <int G, int RB, int H>
+__global__ __launch_bounds__(RB) void occ_raster_kernel(DS d, const int32_t* nodes, int32_t blocks_per_node,
+                                                        int32_t* hits, int32_t* misses, OccCtl* ctl) {
+    constexpr int HS = H > 0 ? H : 1;
+    __shared__ uint32_t keys[HS];
+    __shared__ uint32_t cnt[HS];
+    __shared__ unsigned long long red[6];
+    const int64_t v = nodes[blockIdx.x / blocks_per_node];
+    const int lane = threadIdx.x % G;
+    const int64_t i = (int64_t)(blockIdx.x % blocks_per_node) * (RB / G) + threadIdx.x / G;
+    const int64_t b0 = d.off[v], nb = d.off[v + 1] - b0;
+    const int64_t b = b0 + i;
+    const bool live = i < nb && included(d, v, b);
+    if (!__syncthreads_or(live)) return;      // inactive node, inactive sectors or past the scan's end
+    for (int q = threadIdx.x; q < HS; q += RB) { keys[q] = kEmpty; cnt[q] = 0u; }
+    if (threadIdx.x < 6) red[threadIdx.x] = 0;
+    __syncthreads();
+    unsigned long long ns = 0, oob = 0, nh = 0, direct = 0, flushed = 0;
+    if (live) {
+        const float4 f = d.frame[2 * v];
+        const float2 m = map_point(d, v, b);
+        const uint8_t l = d.label[b];
+        int64_t c, hit_cell = -1;
+        if (l != DPG_LABEL_MAX_RANGE && l != DPG_LABEL_REMOVED) {
+            if (cell_of(d, m.x, m.y, &c)) {
+                hit_cell = c;
+                if (lane == 0) { occ_add<H>(keys, cnt, hits, misses, c, true, &direct); ++nh; }
+            } else if (lane == 0) {
+                ++oob;
+            }
+        }
+        const uint32_t nbins = (uint32_t)round((double)d.range[b] / d.res);
+        const float inc = (float)(1.0 / (double)nbins);
+        // lane l takes the l-th contiguous chunk of the steps, as in raster_kernel
+        const uint32_t chunk = (nbins + G) / G;
+        const uint32_t s0 = (uint32_t)lane * chunk, s1 = lane == G - 1 ? 0xffffffffu : s0 + chunk;
+        uint32_t step = 0;
+        float t = 0.0f;
+        for (; step < s0 && (double)t < 1.0; ++step) t = t + inc;
+        for (; step < s1 && (double)t < 1.0; t = t + inc, ++step) {
+            const float ix = (1 - t) * f.x + t * m.x;
+            const float iy = (1 - t) * f.y + t * m.y;
+            ++ns;
+            if (!cell_of(d, ix, iy, &c)) { ++oob; continue; }
+            if (c == hit_cell) continue;      // the beam's own hit cell is not also a miss
+            occ_add<H>(keys, cnt, hits, misses, c, false, &direct);
+        }
+    }
+    __syncthreads();
+    if (H > 0)
+        for (int q = threadIdx.x; q < HS; q += RB) {
+            const uint32_t key = keys[q];
+            if (key == kEmpty) continue;
+            atomicAdd(((key & 1u) ? hits : misses) + (key >> 1), (int32_t)cnt[q]);
+            ++flushed;
+        }
+    if (ns) atomicAdd(&red[0], ns);
+    if (oob) atomicAdd(&red[1], oob);
+    if (nh) atomicAdd(&red[2], nh);
+    if (direct) atomicAdd(&red[3], direct);
+    if (flushed) atomicAdd(&red[4], flushed);
+    if (live && lane == 0) atomicAdd(&red[5], 1ull);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (red[0]) atomicAdd(&ctl->samples, red[0]);
+        if (red[1]) atomicAdd(&ctl->oob, red[1]);
+        if (red[2]) atomicAdd(&ctl->hits, red[2]);
+        if (red[3]) atomicAdd(&ctl->direct, red[3]);
+        if (red[4]) atomicAdd(&ctl->flushed, red[4]);
+        if (red[5]) atomicAdd(&ctl->beams, red[5]);
+    }
+}
+
+__device__ __forceinline__ uint32_t occ_byte(int32_t h, int32_t m) {
+    const int64_t n = (int64_t)h + m;
+    return n == 0 ? 0xffu : (uint32_t)((200 * (int64_t)h + n) / (2 * n));
+}
+
+__device__ __forceinline__ uint32_t occ_word(int4 h, int4 m) {
+    return occ_byte(h.x, m.x) | (occ_byte(h.y, m.y) << 8) | (occ_byte(h.z, m.z) << 16) | (occ_byte(h.w, m.w) << 24);
+}
+
+// hits, misses -> occupancy bytes, 16 cells per thread and one 16-byte store (the three buffers
+// start on 256-B boundaries)
+__global__ __launch_bounds__(kT) void occ_finalize_kernel(const int32_t* hits, const int32_t* misses, int8_t* occ,
+                                                          int64_t n) {
+    const int64_t stride = (int64_t)gridDim.x * kT, n16 = n >> 4;
+    const int4* h4 = reinterpret_cast<const int4*>(hits);
+    const int4* m4 = reinterpret_cast<const int4*>(misses);
+    uint4* o4 = reinterpret_cast<uint4*>(occ);
+    for (int64_t c = (int64_t)blockIdx.x * kT + threadIdx.x; c < n16; c += stride)
+        o4[c] = make_uint4(occ_word(h4[4 * c], m4[4 * c]), occ_word(h4[4 * c + 1], m4[4 * c + 1]),
+                           occ_word(h4[4 * c + 2], m4[4 * c + 2]), occ_word(h4[4 * c + 3], m4[4 * c + 3]));
+    for (int64_t c = 16 * n16 + (int64_t)blockIdx.x * kT + threadIdx.x; c < n; c += stride)
+        occ[c] = (int8_t)occ_byte(hits[c], misses[c]);
+}
+
+// dpg_dpg_beam_geometry: one thread per beam (its node by bisection of the offsets) and per node
+__global__ __launch_bounds__(kT) void beam_geometry_kernel(DS d, int64_t V, int64_t n_beams, float2* lidar_xy,
+                                                           float2* end_xy) {
+    const int64_t b = (int64_t)blockIdx.x * kT + threadIdx.x;
+    if (lidar_xy && b < V) {
+        const float4 f = d.frame[2 * b];
+        lidar_xy[b] = make_float2(f.x, f.y);
+    }
+    if (!end_xy || b >= n_beams) return;
+    int64_t lo = 0, hi = V;                    // off[lo] <= b < off[hi]
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (d.off[mid] <= b) lo = mid;
+        else hi = mid;
+    }
+    end_xy[b] = map_point(d, lo, b);
+}
+
 // math_utils::AngleMod<float> (math_utils.h:13-16)
 float angle_mod_f(float a) {
     double ad = (double)a;
@@ -581,6 +723,11 @@ struct dpg_dpg {
     DevBuf<float2> d_removed, d_map_out;
     DevBuf<Ctl> d_ctl;
     DevBuf<int64_t> d_counts, d_base;
+    // dpg_occupancy_grid / dpg_dpg_beam_geometry: buffers of their own, empty until the first request
+    DevBuf<int32_t> d_occ_cnt, d_occ_nodes;   // [hits | misses], the active node list
+    DevBuf<int8_t> d_occ_out;
+    DevBuf<OccCtl> d_occ_ctl;
+    DevBuf<float2> d_geo;                     // [lidar positions | end points]
     Ctl* h_ctl = nullptr;             // pinned
     hipEvent_t ev[2] = {};
 };
@@ -1084,6 +1231,38 @@ int finish_call(dpg_dpg* d, int64_t V, int64_t chain_n, double t0, dpg_change_st
     return DPG_OK;
 }
 
+// occ_raster_kernel's lane group / workgroup / LDS table slots.  Variant 0 is the product: 8 lanes per
+// beam, 128 beams per 1024-thread workgroup, 8192 slots (64 KB, two workgroups per CU).  A wave's time
+// is the t chain of its longest beam whatever the lane group, so the kernel's time falls with the
+// number of waves, i.e. with the lane group, until the workgroup's beams overflow the table.  The
+// other variants exist for tools/occ_grid_probe.py (DESIGN.md K7 holds what was measured) and give
+// the same grid.
+template <int G, int RB, int H>
+void occ_launch(const DS& ds, const int32_t* nodes, int64_t n_nodes, int32_t max_beams, int32_t* hits,
+                int32_t* misses, OccCtl* ctl, hipStream_t s) {
+    const int32_t bpn = (max_beams + RB / G - 1) / (RB / G);
+    occ_raster_kernel<G, RB, H><<<(unsigned)(n_nodes * bpn), RB, 0, s>>>(ds, nodes, bpn, hits, misses, ctl);
+}
+
+constexpr int kOccVariants = 10;
+constexpr int kOccBeamsMin = 1024 / 32;   // fewest beams per workgroup among the variants (grid size bound)
+
+void occ_launch_variant(int variant, const DS& ds, const int32_t* nodes, int64_t n, int32_t mb, int32_t* hits,
+                        int32_t* misses, OccCtl* ctl, hipStream_t s) {
+    switch (variant) {
+        case 1: occ_launch<32, 1024, 8192>(ds, nodes, n, mb, hits, misses, ctl, s); break;   // raster_kernel's split
+        case 2: occ_launch<16, 1024, 8192>(ds, nodes, n, mb, hits, misses, ctl, s); break;
+        case 3: occ_launch<8, 1024, 8192>(ds, nodes, n, mb, hits, misses, ctl, s); break;
+        case 4: occ_launch<4, 1024, 8192>(ds, nodes, n, mb, hits, misses, ctl, s); break;
+        case 5: occ_launch<8, 512, 4096>(ds, nodes, n, mb, hits, misses, ctl, s); break;
+        case 6: occ_launch<16, 512, 4096>(ds, nodes, n, mb, hits, misses, ctl, s); break;
+        case 7: occ_launch<32, 1024, 0>(ds, nodes, n, mb, hits, misses, ctl, s); break;   // no table: every add global
+        case 8: occ_launch<8, 512, 8192>(ds, nodes, n, mb, hits, misses, ctl, s); break;
+        case 9: occ_launch<4, 512, 4096>(ds, nodes, n, mb, hits, misses, ctl, s); break;
+        default: occ_launch<8, 1024, 8192>(ds, nodes, n, mb, hits, misses, ctl, s); break;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1153,6 +1332,113 @@ int64_t dpg_active_dynamic_points(dpg_dpg* d, int64_t V, const float* est, float
     DTRY(hipMemcpyAsync(out, d->d_map_out.p, sizeof(float2) * std::min(cap, total), hipMemcpyDeviceToHost, s));
     DTRY(hipStreamSynchronize(s));
     return total;
+}
+
+int dpg_occupancy_grid(dpg_dpg* d, int64_t V, const float* est, const dpg_grid_params* gp, int32_t* hits,
+                       int32_t* misses, int8_t* occ, int64_t cap, dpg_grid_info* info) {
+    if (!d || !est || V <= 0 || V > d->V) return dpg_set_error(DPG_ERR_ARG, "bad arguments");
+    dpg_grid_params p;
+    if (gp) p = *gp;
+    else dpg_grid_params_default(&p);
+    const double res = p.resolution == 0.0 ? d->p.occ_grid_resolution : p.resolution;
+    const int64_t max_cells = p.max_cells == 0 ? (int64_t)1 << 25 : p.max_cells;
+    if (!(res > 0.0) || !std::isfinite(res) || max_cells < 0 || max_cells > (int64_t)1 << 25 || p.margin_cells < 0 ||
+        p.pad < 0 || p.pad >= kOccVariants)
+        return dpg_set_error(DPG_ERR_ARG, "grid params out of range (resolution > 0, max_cells <= 2^25, margin >= 0)");
+    const double t0 = now_ms();
+    dpg_grid_info local;
+    if (!info) info = &local;
+    memset(info, 0, sizeof(*info));
+    info->resolution = res;
+    DTRY(hipSetDevice(d->device));
+    hipStream_t s = d->s;
+    int rc = upload_frames(d, V, est, true);
+    if (rc) return rc;
+    // the box over the active nodes (host mirror of the activity, the cached lidar positions)
+    std::vector<float> lidar((size_t)(2 * V));
+    std::vector<int32_t> nodes;
+    for (int64_t v = 0; v < V; ++v) {
+        lidar[(size_t)(2 * v)] = d->h_frames[8 * v];
+        lidar[(size_t)(2 * v + 1)] = d->h_frames[8 * v + 1];
+        if (d->active_h[(size_t)v]) nodes.push_back((int32_t)v);
+    }
+    int32_t bx[4];
+    rc = dpg_grid_box(lidar.data(), d->rmax_beam.data(), d->active_h.data(), V, res, p.margin_cells, bx);
+    if (rc == DPG_ERR_ARG) return dpg_set_error(rc, "non-finite pose or range of an active node");
+    if (rc) return dpg_set_error(rc, "occupancy grid box exceeds the key range");
+    const int64_t cells = (int64_t)bx[2] * bx[3];
+    if (cells > max_cells) return dpg_set_error(DPG_ERR_SIZE, "occupancy grid box exceeds max_cells");
+    info->x0 = bx[0]; info->y0 = bx[1]; info->w = bx[2]; info->h = bx[3];
+    info->n_nodes_used = (int64_t)nodes.size();
+    if (!hits && !misses && !occ) { info->ms_total = now_ms() - t0; return DPG_OK; }   // plan only
+    if (cap < cells) return dpg_set_error(DPG_ERR_SIZE, "output arrays hold fewer than w * h cells");
+    if (cells == 0) { info->ms_total = now_ms() - t0; return DPG_OK; }
+    const int64_t n = (int64_t)nodes.size();
+    if (n * ((d->max_beams + kOccBeamsMin - 1) / kOccBeamsMin) > (int64_t)INT32_MAX)
+        return dpg_set_error(DPG_ERR_SIZE, "too many active scans for one launch");
+    const int64_t pitch = (cells + 63) & ~(int64_t)63;   // misses start on a 256-B boundary
+    if (d->d_occ_cnt.reserve((size_t)(2 * pitch)) || d->d_occ_out.reserve((size_t)cells) ||
+        d->d_occ_nodes.reserve((size_t)n) || d->d_occ_ctl.reserve(1))
+        return dpg_set_error(DPG_ERR_HIP, "hipMalloc(occupancy grid) failed");
+    DS ds = make_ds(d);
+    ds.res = res;
+    ds.inv_res = 1.0 / res;
+    ds.box = Box{bx[0], bx[1], bx[2], bx[3]};
+    int32_t* dh = d->d_occ_cnt.p;
+    int32_t* dm = d->d_occ_cnt.p + pitch;
+    DTRY(hipMemcpyAsync(d->d_occ_nodes.p, nodes.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
+    DTRY(hipEventRecord(d->ev[0], s));
+    DTRY(hipMemsetAsync(d->d_occ_cnt.p, 0, sizeof(int32_t) * 2 * pitch, s));
+    DTRY(hipMemsetAsync(d->d_occ_ctl.p, 0, sizeof(OccCtl), s));
+    occ_launch_variant(p.pad, ds, d->d_occ_nodes.p, n, d->max_beams, dh, dm, d->d_occ_ctl.p, s);
+    DTRY(hipGetLastError());
+    if (occ) {
+        occ_finalize_kernel<<<(unsigned)std::min<int64_t>((cells / 16 + kT) / kT, 2048), kT, 0, s>>>(dh, dm, d->d_occ_out.p, cells);
+        DTRY(hipGetLastError());
+    }
+    DTRY(hipEventRecord(d->ev[1], s));
+    // the outputs are staged so that a failure before this point leaves the caller's arrays untouched
+    OccCtl c;
+    DTRY(hipMemcpyAsync(&c, d->d_occ_ctl.p, sizeof(c), hipMemcpyDeviceToHost, s));
+    DTRY(hipStreamSynchronize(s));
+    if (hits) DTRY(hipMemcpyAsync(hits, dh, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, s));
+    if (misses) DTRY(hipMemcpyAsync(misses, dm, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, s));
+    if (occ) DTRY(hipMemcpyAsync(occ, d->d_occ_out.p, (size_t)cells, hipMemcpyDeviceToHost, s));
+    DTRY(hipStreamSynchronize(s));
+    info->n_beams_used = (int64_t)c.beams;
+    info->n_hits = (int64_t)c.hits;
+    info->n_samples = (int64_t)c.samples;
+    info->n_oob = (int64_t)c.oob;
+    info->n_direct = (int64_t)c.direct;
+    info->n_flushed = (int64_t)c.flushed;
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, d->ev[0], d->ev[1]);
+    info->ms_kernels = ms;
+    info->ms_total = now_ms() - t0;
+    return DPG_OK;
+}
+
+int dpg_dpg_beam_geometry(dpg_dpg* d, int64_t V, const float* est, float* lidar_xy, float* end_xy, int64_t cap_beams) {
+    if (!d || !est || V <= 0 || V > d->V) return dpg_set_error(DPG_ERR_ARG, "bad arguments");
+    const int64_t nB = d->off[(size_t)V];
+    if (end_xy && cap_beams < nB) return dpg_set_error(DPG_ERR_SIZE, "end_xy holds fewer beams than the nodes have");
+    if (!lidar_xy && !end_xy) return DPG_OK;
+    DTRY(hipSetDevice(d->device));
+    hipStream_t s = d->s;
+    int rc = upload_frames(d, V, est);
+    if (rc) return rc;
+    if (d->d_geo.reserve((size_t)(V + nB))) return dpg_set_error(DPG_ERR_HIP, "hipMalloc(beam geometry) failed");
+    float2* dl = d->d_geo.p;
+    float2* de = d->d_geo.p + V;
+    const DS ds = make_ds(d);
+    const int64_t threads = std::max(V, nB);
+    beam_geometry_kernel<<<(unsigned)((threads + kT - 1) / kT), kT, 0, s>>>(ds, V, nB, lidar_xy ? dl : nullptr,
+                                                                            end_xy ? de : nullptr);
+    DTRY(hipGetLastError());
+    if (lidar_xy) DTRY(hipMemcpyAsync(lidar_xy, dl, sizeof(float2) * V, hipMemcpyDeviceToHost, s));
+    if (end_xy) DTRY(hipMemcpyAsync(end_xy, de, sizeof(float2) * nB, hipMemcpyDeviceToHost, s));
+    DTRY(hipStreamSynchronize(s));
+    return DPG_OK;
 }
 
 }  // extern "C"

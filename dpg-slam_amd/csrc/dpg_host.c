@@ -123,6 +123,48 @@ void dpg_gn_params_default(dpg_gn_params* p) {
     p->refactor_delta = 1e-3;
 }
 
+void dpg_grid_params_default(dpg_grid_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->margin_cells = 1;
+}
+
+/* occupancy byte of a cell: unknown (-1) without an observation, else 100 hits / n rounded half up */
+void dpg_occupancy_from_counts(const int32_t* hits, const int32_t* misses, int64_t n, int8_t* occ) {
+    for (int64_t c = 0; c < n; ++c) {
+        const int64_t h = hits[c], t = h + (int64_t)misses[c];
+        occ[c] = t == 0 ? (int8_t)-1 : (int8_t)((200 * h + t) / (2 * t));
+    }
+}
+
+/* the grid's box: every ray of an active node stays within the node's largest range of its lidar */
+int dpg_grid_box(const float* lidar_xy, const float* r_v, const uint8_t* active, int64_t n, double res,
+                 int32_t margin, int32_t box[4]) {
+    if (!box || n < 0 || (n > 0 && (!lidar_xy || !r_v)) || !(res > 0.0) || !isfinite(res) || margin < 0)
+        return DPG_ERR_ARG;
+    double xlo = INFINITY, xhi = -INFINITY, ylo = INFINITY, yhi = -INFINITY;
+    int any = 0;
+    for (int64_t v = 0; v < n; ++v) {
+        if (active && !active[v]) continue;
+        const double x = (double)lidar_xy[2 * v], y = (double)lidar_xy[2 * v + 1], r = (double)r_v[v];
+        if (!isfinite(x) || !isfinite(y) || !isfinite(r)) return DPG_ERR_ARG;
+        any = 1;
+        xlo = fmin(xlo, x - r); xhi = fmax(xhi, x + r);
+        ylo = fmin(ylo, y - r); yhi = fmax(yhi, y + r);
+    }
+    box[0] = box[1] = box[2] = box[3] = 0;
+    if (!any) return DPG_OK;
+    const double lim = 536870912.0; /* 2^29: keys and sides stay inside int32 */
+    const double x0 = floor(xlo / res) - margin, x1 = ceil(xhi / res) + margin;
+    const double y0 = floor(ylo / res) - margin, y1 = ceil(yhi / res) + margin;
+    if (x0 < -lim || y0 < -lim || x1 > lim || y1 > lim) return DPG_ERR_SIZE;
+    box[0] = (int32_t)x0;
+    box[1] = (int32_t)y0;
+    box[2] = (int32_t)(x1 - x0 + 1.0);
+    box[3] = (int32_t)(y1 - y0 + 1.0);
+    return DPG_OK;
+}
+
 /* R9: odometry BetweenFactor from two odom_only_estimates (dpg_slam.cc:56-75). */
 int dpg_odometry_factor(const float odom_prev[3], const float odom_cur[3], int32_t i_prev, int32_t i_cur,
                         float transl_from_transl, float transl_from_rot, float rot_from_transl,

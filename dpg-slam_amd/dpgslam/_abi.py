@@ -187,6 +187,7 @@ F64P = C.POINTER(C.c_double)
 I32P = C.POINTER(C.c_int32)
 I64P = C.POINTER(C.c_int64)
 U8P = C.POINTER(C.c_uint8)
+I8P = C.POINTER(C.c_int8)
 
 # name -> (restype, argtypes); the full exported surface of include/*.h
 
@@ -221,6 +222,23 @@ class ChangeStats(C.Structure):
 
     def counters(self) -> dict:
         return {k: int(getattr(self, k)) for k in self.COUNTERS}
+
+
+class GridParams(C.Structure):
+    """dpg_grid_params -- resolution, size bound and margin of dpg_occupancy_grid."""
+
+    _fields_ = [("resolution", C.c_double), ("max_cells", C.c_int64), ("margin_cells", C.c_int32), ("pad", C.c_int32)]
+
+
+class GridInfo(C.Structure):
+    """dpg_grid_info -- the box, counters and timings of one dpg_occupancy_grid."""
+
+    _fields_ = [(n, C.c_int32) for n in ("x0", "y0", "w", "h")] + [("resolution", C.c_double)] + [
+        (n, C.c_int64) for n in ("n_nodes_used", "n_beams_used", "n_hits", "n_samples", "n_oob")] + [
+        ("ms_total", C.c_double), ("ms_kernels", C.c_double), ("n_direct", C.c_int64), ("n_flushed", C.c_int64)]
+
+    def as_dict(self) -> dict:
+        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 ALLREDUCE_F64 = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int64)
@@ -333,6 +351,12 @@ SIGNATURES = {
     "dpg_dpg_fetch": (C.c_int, [P, U8P, U8P, U8P]),
     "dpg_dpg_load": (C.c_int, [P, U8P, U8P, U8P]),
     "dpg_active_dynamic_points": (C.c_int64, [P, C.c_int64, F32P, F32P, C.c_int64, I64P]),
+    "dpg_grid_params_default": (None, [C.POINTER(GridParams)]),
+    "dpg_occupancy_grid": (C.c_int, [P, C.c_int64, F32P, C.POINTER(GridParams), I32P, I32P, I8P, C.c_int64,
+                                     C.POINTER(GridInfo)]),
+    "dpg_dpg_beam_geometry": (C.c_int, [P, C.c_int64, F32P, F32P, F32P, C.c_int64]),
+    "dpg_occupancy_from_counts": (None, [I32P, I32P, C.c_int64, I8P]),
+    "dpg_grid_box": (C.c_int, [F32P, F32P, U8P, C.c_int64, C.c_double, C.c_int32, I32P]),
     "dpg_reoptimize": (C.c_int, [P, C.c_int64, I32P, F32P, F32P, C.POINTER(IcpParams), C.POINTER(GnParams),
                                  C.POINTER(ReoptParams), F64P, C.POINTER(ReoptStats)]),
     "dpg_reoptimize_inc": (C.c_int, [P, C.c_int64, I32P, F32P, F32P, C.POINTER(IcpParams), C.POINTER(ReoptParams),
@@ -439,6 +463,12 @@ def default_change_params() -> ChangeParams:
 
 
 default_change_params_host = default_change_params
+
+
+def default_grid_params() -> GridParams:
+    p = GridParams()
+    lib().dpg_grid_params_default(C.byref(p))
+    return p
 
 
 def default_gn_params() -> GnParams:

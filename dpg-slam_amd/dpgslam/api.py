@@ -631,6 +631,7 @@ class DpgStore:
         off = np.ascontiguousarray(offsets, np.int64)
         self.V = len(off) - 1
         self.B = int(off[-1])
+        self.offsets = off.copy()   # beam offsets of every node so far
         g = _f32(geom).reshape(self.V, 3)
         self.params = params or _abi.default_change_params()
         self.ctx = ctx
@@ -665,6 +666,7 @@ class DpgStore:
         check(lib().dpg_dpg_append(self.handle, len(off) - 1, ptr(off, C.c_int64), ptr(r.reshape(-1), C.c_float),
                                    ptr(g, C.c_float)), "dpg_dpg_append")
         self.V += len(off) - 1
+        self.offsets = np.concatenate([self.offsets, self.B + (off[1:] - off[0])])
         self.B += int(off[-1] - off[0])
 
     def execute_dpg(self, n_nodes: int, current_pass_len: int, est, chain_poses=None) -> "_abi.ChangeStats":
@@ -713,6 +715,40 @@ class DpgStore:
             res[name] = out[k:k + c].copy()
             k += int(c)
         return res
+
+    def occupancy_grid(self, n_nodes: int, est, params=None, counts=False):
+        """The occupancy grid of the active nodes of [0, n_nodes) at est (dpg_occupancy_grid): dict of
+        `resolution`, `origin` (x, y of the lower-left corner of cell (0, 0)), `width`, `height` and
+        `data` (int8 [height, width]: -1 unknown, else 0..100); with counts=True also `hits`, `misses`
+        (int32 [height, width]) and `info` (GridInfo).  One call plans the box, a second fills it."""
+        e = _f32(est).reshape(-1, 3)
+        p = params or _abi.default_grid_params()
+        info = _abi.GridInfo()
+        check(lib().dpg_occupancy_grid(self.handle, n_nodes, ptr(e, C.c_float), C.byref(p), None, None, None, 0,
+                                       C.byref(info)), "dpg_occupancy_grid")
+        h, w = int(info.h), int(info.w)
+        data = np.zeros((h, w), np.int8)
+        hits = np.zeros((h, w), np.int32) if counts else None
+        misses = np.zeros((h, w), np.int32) if counts else None
+        check(lib().dpg_occupancy_grid(self.handle, n_nodes, ptr(e, C.c_float), C.byref(p), ptr(hits, C.c_int32),
+                                       ptr(misses, C.c_int32), ptr(data, C.c_int8), h * w, C.byref(info)),
+              "dpg_occupancy_grid")
+        res = float(info.resolution)
+        out = {"resolution": res, "origin": ((info.x0 - 0.5) * res, (info.y0 - 0.5) * res), "width": w, "height": h,
+               "data": data}
+        if counts:
+            out.update(hits=hits, misses=misses, info=info)
+        return out
+
+    def beam_geometry(self, n_nodes: int, est):
+        """(lidar_xy [n_nodes, 2], end_xy [beams, 2]): each node's lidar position in the map and each
+        beam's end point, as the device computes them (dpg_dpg_beam_geometry)."""
+        e = _f32(est).reshape(-1, 3)
+        lidar = np.zeros((n_nodes, 2), np.float32)
+        end = np.zeros((self.B, 2), np.float32)
+        check(lib().dpg_dpg_beam_geometry(self.handle, n_nodes, ptr(e, C.c_float), ptr(lidar, C.c_float),
+                                          ptr(end, C.c_float), self.B), "dpg_dpg_beam_geometry")
+        return lidar, end[:int(self.offsets[n_nodes])]
 
 
 class IncGraph:

@@ -226,6 +226,26 @@ class DpgSLAM:
         """getActiveAndDynamicMapPoints (dpg_slam.cc:832-863) over the current node state."""
         return self._dpg_store().active_dynamic_points(len(self.poses), self.poses)
 
+    def GetOccupancyGrid(self, resolution=None):
+        """The occupancy grid of the active pose graph over the current node state -- the fields of a
+        nav_msgs/OccupancyGrid: dict of `resolution`, `origin` (x, y), `width`, `height` and `data`
+        (int8 [height, width]: -1 unknown, 0..100 occupancy).  resolution None: the
+        change detection's occ_grid_resolution.  The reference only hands back point lists."""
+        V = len(self.poses)
+        if V == 0:
+            raise ValueError("GetOccupancyGrid: the graph has no node yet")
+        if resolution is not None and not float(resolution) > 0.0:
+            raise ValueError(f"GetOccupancyGrid: resolution must be positive, got {resolution!r}")
+        store = self._dpg_store()
+        fn = getattr(store, "occupancy_grid", None)
+        if fn is None:
+            raise NotImplementedError(f"GetOccupancyGrid needs an `occupancy_grid(n_nodes, est, params)` method on the "
+                                      f"backend's node store; {type(store).__name__} has none")
+        p = _abi.default_grid_params()
+        if resolution is not None:
+            p.resolution = float(resolution)
+        return fn(V, self.poses, p)
+
     def executeDPG(self):
         """dpg_slam.cc:865-886 (dpg_execute_dpg on the node store)."""
         return self._dpg_store().execute_dpg(len(self.poses), len(self.current_pass), self.poses)

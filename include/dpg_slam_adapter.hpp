@@ -362,6 +362,26 @@ class DpgStore {
         return run(nodes, current_pass_nodes.size(), &current_pass_nodes, active_static, active_added,
                    dynamic_removed, dynamic_added);
     }
+    /* the occupancy grid of the active nodes at their current poses (dpg_occupancy_grid): data_out
+       becomes the row-major int8 [info_out.h][info_out.w] array of a nav_msgs/OccupancyGrid (-1
+       unknown, 0..100), whose origin is ((x0 - 0.5) resolution, (y0 - 0.5) resolution); resolution 0
+       is the change detection's occ_grid_resolution */
+    template <class NodeVec>
+    void occupancyGrid(const NodeVec& nodes, double resolution, std::vector<int8_t>& data_out, dpg_grid_info& info_out) {
+        const size_t V = nodes.size();
+        if (!d_ || V == 0) throw Error("occupancyGrid: no scan added yet");
+        std::vector<float> est(3 * V);
+        for (size_t i = 0; i < V; ++i) pose_of(nodes[i], &est[3 * i]);
+        dpg_grid_params gp;
+        dpg_grid_params_default(&gp);
+        gp.resolution = resolution;
+        check(dpg_occupancy_grid(d_, (int64_t)V, est.data(), &gp, nullptr, nullptr, nullptr, 0, &info_out),
+              "dpg_occupancy_grid");
+        const int64_t cells = (int64_t)info_out.w * info_out.h;
+        data_out.assign((size_t)cells, (int8_t)-1);
+        check(dpg_occupancy_grid(d_, (int64_t)V, est.data(), &gp, nullptr, nullptr, data_out.data(), cells, &info_out),
+              "dpg_occupancy_grid");
+    }
   private:
     template <class NodeVec, class PointVec>
     dpg_change_stats run(NodeVec& nodes, size_t current_pass_len, const NodeVec* pass_nodes, PointVec& active_static,

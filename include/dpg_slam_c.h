@@ -747,6 +747,81 @@ int dpg_dpg_load(dpg_dpg* d, const uint8_t* labels, const uint8_t* sector_active
 int64_t dpg_active_dynamic_points(dpg_dpg* d, int64_t n_nodes, const float* est_poses, float* out,
                                   int64_t cap, int64_t counts[4]);
 
+/* ---- Occupancy grid of the active pose graph (nav_msgs/OccupancyGrid: free, occupied, unknown) ----
+ * The counting form of the change detection's rasteriser over every active node of [0, n_nodes) at
+ * est_poses, at a resolution of its own.
+ *   Included beams: exactly the beams executeDPG rasterises -- the node is active and the beam's
+ *     sector is active.
+ *   Cell key of a coordinate v: round((double)v / res), C round (halves away from zero).
+ *   Free samples of a beam with lidar position f (the node's lidar in the map) and end point m:
+ *     nbins = (uint32)round((double)range / res), inc = (float)(1.0 / (double)nbins), t = 0.0f;
+ *     while ((double)t < 1.0) the sample is ((1 - t) * f.x + t * m.x, (1 - t) * f.y + t * m.y) in float
+ *     without contraction, then t = t + inc (getIntermediateFreeCellsInFOV, dpg_slam.cc:1059-1082).
+ *   hits[c]:   included beams whose label is neither DPG_LABEL_MAX_RANGE nor DPG_LABEL_REMOVED and
+ *     whose end point m falls in cell c.
+ *   misses[c]: free samples of included beams (every label) that fall in c, except a sample in its
+ *     own beam's end-point cell when that end point counted as a hit (otherwise every wall cell would
+ *     read about 50 %).
+ *   occ[c]: with n = hits + misses, -1 when n == 0, else (200 * hits + n) / (2 * n) in integer
+ *     arithmetic: 100 * hits / n rounded half up, 0..100.
+ *   Box (host, fp64, over the active nodes; r_v = the node's largest range, (lx_v, ly_v) its lidar):
+ *     x0 = floor(min_v(lx_v - r_v) / res) - margin, x1 = ceil(max_v(lx_v + r_v) / res) + margin,
+ *     y0, y1 alike, w = x1 - x0 + 1, h = y1 - y0 + 1; no active node: w = h = 0 and the call succeeds.
+ *     Cell (ix, iy) has key (x0 + ix, y0 + iy); the arrays are row-major [h][w]; the lower-left corner
+ *     of cell (0, 0) lies at ((x0 - 0.5) * res, (y0 - 0.5) * res) in the map frame.
+ * All accumulation is integer and order-free: two calls on the same state are bitwise equal.  The
+ * call reads the store and refreshes its cached node frames, nothing else: labels, sectors, activity,
+ * the change-detection window and its kept chain planes stay as they are.  Its device buffers are its
+ * own, allocated at the first request and regrown only when a request needs more. */
+typedef struct dpg_grid_params {
+    double resolution;     /* m per cell; 0 = the store's occ_grid_resolution */
+    int64_t max_cells;     /* 0 = 1 << 25 (also the largest value); a larger box is DPG_ERR_SIZE */
+    int32_t margin_cells;  /* default 1 */
+    int32_t pad;           /* 0; 1..9 run a measurement variant of the raster kernel (same result,
+                              DESIGN.md K7, tools/occ_grid_probe.py) */
+} dpg_grid_params;
+
+typedef struct dpg_grid_info {
+    int32_t x0, y0, w, h;
+    double resolution;
+    int64_t n_nodes_used;  /* active nodes */
+    int64_t n_beams_used;  /* included beams */
+    int64_t n_hits;        /* sum of hits[] */
+    int64_t n_samples;     /* free samples marched (those dropped in their beam's hit cell included) */
+    int64_t n_oob;         /* end points and samples outside the box: 0 by construction */
+    double ms_total, ms_kernels;
+    int64_t n_direct;      /* adds that found no slot in a workgroup's LDS table and went straight to the global counter */
+    int64_t n_flushed;     /* global atomic adds issued when the LDS tables were flushed */
+} dpg_grid_info;
+
+#define DPG_GRID_PARAMS_SIZE 24
+#define DPG_GRID_INFO_SIZE 96
+#ifdef __cplusplus
+ static_assert(sizeof(dpg_grid_params) == DPG_GRID_PARAMS_SIZE && sizeof(dpg_grid_info) == DPG_GRID_INFO_SIZE, "grid ABI structs");
+#else
+ _Static_assert(sizeof(dpg_grid_params) == DPG_GRID_PARAMS_SIZE && sizeof(dpg_grid_info) == DPG_GRID_INFO_SIZE, "grid ABI structs");
+#endif
+
+void dpg_grid_params_default(dpg_grid_params* p);
+/* The grid.  hits, misses [cap] int32 and occ [cap] int8 may each be NULL.  With all three NULL the
+ * call only plans: info receives the box and nothing is launched.  Any non-NULL output with
+ * cap < w * h is DPG_ERR_SIZE with nothing written.  info may be NULL. */
+int dpg_occupancy_grid(dpg_dpg* d, int64_t n_nodes, const float* est_poses, const dpg_grid_params* p,
+                       int32_t* hits, int32_t* misses, int8_t* occ, int64_t cap, dpg_grid_info* info);
+/* Each node's lidar position in the map frame, lidar_xy[n_nodes][2], and each beam's end point,
+ * end_xy[B][2] with B = the beams of nodes [0, n_nodes), as the device computes them (every node and
+ * beam, whatever its state).  Either pointer may be NULL; cap_beams < B with end_xy given is
+ * DPG_ERR_SIZE with nothing written. */
+int dpg_dpg_beam_geometry(dpg_dpg* d, int64_t n_nodes, const float* est_poses, float* lidar_xy, float* end_xy,
+                          int64_t cap_beams);
+/* Host: the occupancy byte of n cells from their counters (the formula above). */
+void dpg_occupancy_from_counts(const int32_t* hits, const int32_t* misses, int64_t n, int8_t* occ);
+/* Host: the box rule above over n nodes (lidar_xy[n][2], largest range r_v[n], active[n]; active ==
+ * NULL: all): box = x0, y0, w, h.  DPG_ERR_ARG: res not a positive number, margin < 0 or a
+ * non-finite input of an active node; DPG_ERR_SIZE: a cell key beyond +-2^29. */
+int dpg_grid_box(const float* lidar_xy, const float* r_v, const uint8_t* active, int64_t n, double res,
+                 int32_t margin, int32_t box[4]);
+
 #ifdef __cplusplus
 }
 #endif
