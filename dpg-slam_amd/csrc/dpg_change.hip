@@ -695,16 +695,13 @@ struct dpg_dpg {
     std::vector<float> rmax_beam;     // largest range of each node's beams (window size)
     std::vector<uint8_t> active_h;    // host mirror of the node activity
     std::vector<float> h_pose;        // [V][3] pose bits the cached frames were computed from (NaN: none)
-    float* h_frames = nullptr;        // [V][8] cached node frames, pinned (see upload_frames)
-    int64_t h_cap = 0;                // nodes the pinned mirrors (h_frames, h_act) hold
-    unsigned char* h_app = nullptr;   // pinned staging of dpg_dpg_append's uploads
-    size_t app_cap = 0;
+    PinBuf<float> h_frames;           // [V][8] cached node frames, pinned (see upload_frames)
+    PinBuf<unsigned char> h_app;      // pinned staging of dpg_dpg_append's uploads
     // pinned staging of the per-call inputs/outputs: one H2D copy of [chain 16 | slot 16 | rast 16 |
     // chain frames 128 | candidates], one D2H of the node activity and the commit flags
-    int32_t* h_stage = nullptr;
-    int64_t stage_cap = 0;
-    uint32_t* h_act = nullptr;
-    int32_t* h_commit = nullptr;
+    PinBuf<int32_t> h_stage;
+    PinBuf<uint32_t> h_act;
+    PinBuf<int32_t> h_commit;
     // the window kept across calls: chain grids of nodes still in the chain (same pose) stay as
     // planes; only the new chain node is rasterised (see dpg_execute_dpg)
     Box win{};
@@ -728,8 +725,8 @@ struct dpg_dpg {
     DevBuf<int8_t> d_occ_out;
     DevBuf<OccCtl> d_occ_ctl;
     DevBuf<float2> d_geo;                     // [lidar positions | end points]
-    Ctl* h_ctl = nullptr;             // pinned
-    hipEvent_t ev[2] = {};
+    PinBuf<Ctl> h_ctl;
+    DevEvent ev[2];
 };
 
 #define DTRY(expr)                                                                     \
@@ -785,12 +782,12 @@ int upload_frames(dpg_dpg* d, int64_t V, const float* est, bool active_only = fa
         float* c = &d->h_pose[(size_t)(3 * v)];
         if (memcmp(c, est + 3 * v, 3 * sizeof(float)) == 0) continue;
         memcpy(c, est + 3 * v, 3 * sizeof(float));
-        node_frame(d, est + 3 * v, &d->h_frames[(size_t)(8 * v)]);
+        node_frame(d, est + 3 * v, &d->h_frames.p[(size_t)(8 * v)]);
         lo = std::min(lo, v);
         hi = v;
     }
     if (hi >= lo)
-        DTRY(hipMemcpyAsync(d->d_frame.p + 2 * lo, &d->h_frames[(size_t)(8 * lo)], sizeof(float) * 8 * (hi - lo + 1),
+        DTRY(hipMemcpyAsync(d->d_frame.p + 2 * lo, &d->h_frames.p[(size_t)(8 * lo)], sizeof(float) * 8 * (hi - lo + 1),
                             hipMemcpyHostToDevice, d->s));
     return DPG_OK;
 }
@@ -860,7 +857,7 @@ dpg_dpg* dpg_dpg_create(dpg_ctx* ctx, int64_t V, const int64_t* off, const float
         }
     }
     std::vector<uint32_t> sect((size_t)V, (1u << p->num_sectors) - 1u), act((size_t)V, 1u);
-    // error paths free what was allocated so far (pinned mirrors, events, device buffers)
+    // error paths: d's buffers and events release themselves
     auto bad = [&](const char* m) { dpg_dpg_destroy(d); dpg_set_error(DPG_ERR_HIP, m); return (dpg_dpg*)nullptr; };
     if (hipSetDevice(d->device) != hipSuccess) return bad("hipSetDevice failed");
     if (d->d_off.reserve((size_t)(V + 1)) || d->d_plaser.reserve((size_t)d->B) || d->d_range.reserve((size_t)d->B) ||
@@ -868,13 +865,9 @@ dpg_dpg* dpg_dpg_create(dpg_ctx* ctx, int64_t V, const int64_t* off, const float
         d->d_sect.reserve((size_t)V) || d->d_active.reserve((size_t)V) || d->d_ctl.reserve(1) ||
         d->d_frame.reserve((size_t)(2 * V)))
         return bad("hipMalloc failed");
-    if (hipHostMalloc(reinterpret_cast<void**>(&d->h_ctl), sizeof(Ctl), hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void**>(&d->h_frames), sizeof(float) * 8 * V, hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void**>(&d->h_act), sizeof(uint32_t) * V, hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void**>(&d->h_commit), sizeof(int32_t) * 16, hipHostMallocDefault) != hipSuccess)
+    if (d->h_ctl.reserve(1) || d->h_frames.reserve((size_t)(8 * V)) || d->h_act.reserve((size_t)V) || d->h_commit.reserve(16))
         return bad("hipHostMalloc failed");
-    memset(d->h_frames, 0, sizeof(float) * 8 * V);
-    d->h_cap = V;
+    memset(d->h_frames.p, 0, sizeof(float) * 8 * V);
     hipStream_t s = d->s;
     if (hipMemcpyAsync(d->d_off.p, off, sizeof(int64_t) * (V + 1), hipMemcpyHostToDevice, s) != hipSuccess ||
         hipMemcpyAsync(d->d_plaser.p, pl.data(), sizeof(float2) * d->B, hipMemcpyHostToDevice, s) != hipSuccess ||
@@ -886,7 +879,7 @@ dpg_dpg* dpg_dpg_create(dpg_ctx* ctx, int64_t V, const int64_t* off, const float
         hipMemcpyAsync(d->d_active.p, act.data(), sizeof(uint32_t) * V, hipMemcpyHostToDevice, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)
         return bad("upload of the node store failed");
-    for (auto& e : d->ev) (void)hipEventCreate(&e);
+    for (auto& e : d->ev) (void)e.ensure(hipEventDefault);
     dpg_ctx_adopt(ctx, d, [](void* x) { dpg_dpg_destroy(static_cast<dpg_dpg*>(x)); });
     return d;
 }
@@ -917,16 +910,8 @@ int dpg_dpg_append(dpg_dpg* d, int64_t n_new, const int64_t* off_rel, const floa
                  o_gm = al(o_rg + 4 * (size_t)nb_new), o_sc = al(o_gm + 16 * (size_t)n_new),
                  o_ac = al(o_sc + 4 * (size_t)n_new), o_lb = al(o_ac + 4 * (size_t)n_new), o_sr = al(o_lb + (size_t)nb_new),
                  need = al(o_sr + (size_t)nb_new);
-    if (need > d->app_cap) {
-        unsigned char* nb = nullptr;
-        const size_t cap = std::max(need, d->app_cap + d->app_cap / 2);
-        if (hipHostMalloc(reinterpret_cast<void**>(&nb), cap, hipHostMallocDefault) != hipSuccess)
-            return dpg_set_error(DPG_ERR_HIP, "hipHostMalloc(append staging) failed");
-        if (d->h_app) (void)hipHostFree(d->h_app);
-        d->h_app = nb;
-        d->app_cap = cap;
-    }
-    unsigned char* st = d->h_app;
+    if (d->h_app.grow(need, 0, s)) return dpg_set_error(DPG_ERR_HIP, "hipHostMalloc(append staging) failed");
+    unsigned char* st = d->h_app.p;
     int64_t* off_new = reinterpret_cast<int64_t*>(st + o_off);
     float2* pl = reinterpret_cast<float2*>(st + o_pl);
     float* rg = reinterpret_cast<float*>(st + o_rg);
@@ -963,43 +948,16 @@ int dpg_dpg_append(dpg_dpg* d, int64_t n_new, const int64_t* off_rel, const floa
         act[k] = 1u;
     }
     // device arrays grow with their contents kept (amortised x1.5)
-    auto grow = [&](auto& b, size_t used, size_t need_n) -> int {
-        using T = std::remove_pointer_t<decltype(b.p)>;
-        if (need_n <= b.cap) return 0;
-        const size_t cap = std::max(need_n, b.cap + b.cap / 2);
-        T* np = nullptr;
-        if (hipMalloc(reinterpret_cast<void**>(&np), cap * sizeof(T)) != hipSuccess) return -1;
-        if (used && hipMemcpyAsync(np, b.p, used * sizeof(T), hipMemcpyDeviceToDevice, s) != hipSuccess) { (void)hipFree(np); return -1; }
-        if (hipStreamSynchronize(s) != hipSuccess) { (void)hipFree(np); return -1; }
-        if (b.p) (void)hipFree(b.p);
-        b.p = np;
-        b.cap = cap;
-        return 0;
-    };
     const size_t B1 = (size_t)(B0 + nb_new);
-    if (grow(d->d_off, (size_t)(V0 + 1), (size_t)(V1 + 1)) || grow(d->d_plaser, (size_t)B0, B1) || grow(d->d_range, (size_t)B0, B1) ||
-        grow(d->d_label, (size_t)B0, B1) || grow(d->d_sector, (size_t)B0, B1) || grow(d->d_geom, (size_t)V0, (size_t)V1) ||
-        grow(d->d_sect, (size_t)V0, (size_t)V1) || grow(d->d_active, (size_t)V0, (size_t)V1) ||
-        grow(d->d_frame, (size_t)(2 * V0), (size_t)(2 * V1)))
+    if (d->d_off.grow((size_t)(V1 + 1), (size_t)(V0 + 1), s) || d->d_plaser.grow(B1, (size_t)B0, s) ||
+        d->d_range.grow(B1, (size_t)B0, s) || d->d_label.grow(B1, (size_t)B0, s) || d->d_sector.grow(B1, (size_t)B0, s) ||
+        d->d_geom.grow((size_t)V1, (size_t)V0, s) || d->d_sect.grow((size_t)V1, (size_t)V0, s) ||
+        d->d_active.grow((size_t)V1, (size_t)V0, s) || d->d_frame.grow((size_t)(2 * V1), (size_t)(2 * V0), s))
         return dpg_set_error(DPG_ERR_HIP, "hipMalloc(node store growth) failed");
-    // pinned host mirrors, amortised x1.5
-    if (V1 > d->h_cap) {
-        const int64_t cap = std::max<int64_t>(V1, d->h_cap + d->h_cap / 2);
-        float* nf = nullptr;
-        uint32_t* na = nullptr;
-        if (hipHostMalloc(reinterpret_cast<void**>(&nf), sizeof(float) * 8 * cap, hipHostMallocDefault) != hipSuccess ||
-            hipHostMalloc(reinterpret_cast<void**>(&na), sizeof(uint32_t) * cap, hipHostMallocDefault) != hipSuccess) {
-            if (nf) (void)hipHostFree(nf);
-            return dpg_set_error(DPG_ERR_HIP, "hipHostMalloc(node store growth) failed");
-        }
-        memcpy(nf, d->h_frames, sizeof(float) * 8 * V0);
-        (void)hipHostFree(d->h_frames);
-        (void)hipHostFree(d->h_act);
-        d->h_frames = nf;
-        d->h_act = na;
-        d->h_cap = cap;
-    }
-    memset(d->h_frames + 8 * V0, 0, sizeof(float) * 8 * n_new);
+    // pinned host mirrors, amortised x1.5 (the activity mirror is rewritten by every call)
+    if (d->h_frames.grow((size_t)(8 * V1), (size_t)(8 * V0), s) || d->h_act.grow((size_t)V1, 0, s))
+        return dpg_set_error(DPG_ERR_HIP, "hipHostMalloc(node store growth) failed");
+    memset(d->h_frames.p + 8 * V0, 0, sizeof(float) * 8 * n_new);
     DTRY(hipMemcpyAsync(d->d_off.p + V0 + 1, off_new, sizeof(int64_t) * n_new, hipMemcpyHostToDevice, s));
     DTRY(hipMemcpyAsync(d->d_plaser.p + B0, pl, sizeof(float2) * nb_new, hipMemcpyHostToDevice, s));
     DTRY(hipMemcpyAsync(d->d_range.p + B0, rg, sizeof(float) * nb_new, hipMemcpyHostToDevice, s));
@@ -1024,13 +982,6 @@ void dpg_dpg_destroy(dpg_dpg* d) {
     dpg_ctx_release_child(d->ctx, d);
     (void)hipSetDevice(d->device);
     (void)hipStreamSynchronize(d->s);
-    if (d->h_ctl) (void)hipHostFree(d->h_ctl);
-    if (d->h_frames) (void)hipHostFree(d->h_frames);
-    if (d->h_act) (void)hipHostFree(d->h_act);
-    if (d->h_commit) (void)hipHostFree(d->h_commit);
-    if (d->h_stage) (void)hipHostFree(d->h_stage);
-    if (d->h_app) (void)hipHostFree(d->h_app);
-    for (auto& e : d->ev) if (e) (void)hipEventDestroy(e);
     delete d;
 }
 
@@ -1072,11 +1023,11 @@ int dpg_execute_dpg_chain(dpg_dpg* d, int64_t V, int64_t cur_len, const float* e
     if (d->d_ctl.reserve(1)) return dpg_set_error(DPG_ERR_HIP, "hipMalloc(ctl) failed");
     if (chain_n == 0) {   // no pose chain: only the sector/node update of the (empty) removed set runs
         DS ds = make_ds(d);
-        DTRY(hipEventRecord(d->ev[0], s));
+        DTRY(hipEventRecord(d->ev[0].e, s));
         DTRY(hipMemsetAsync(d->d_ctl.p, 0, sizeof(Ctl), s));
         if (n_past > 0) deactivate_kernel<<<(unsigned)n_past, kT, 0, s>>>(ds);
         DTRY(hipGetLastError());
-        DTRY(hipEventRecord(d->ev[1], s));
+        DTRY(hipEventRecord(d->ev[1].e, s));
         return finish_call(d, V, 0, t0, st);
     }
     // window: every chain ray stays within its longest range of the lidar
@@ -1147,24 +1098,17 @@ int dpg_execute_dpg_chain(dpg_dpg* d, int64_t V, int64_t cur_len, const float* e
     }
     const int64_t nc = (int64_t)cand.size();
     const int32_t bin_words = (p.num_bins_for_change_detection + 2 + 31) / 32;
-    if (d->stage_cap < kStageCand + nc) {
-        if (d->h_stage) (void)hipHostFree(d->h_stage);
-        d->h_stage = nullptr;
-        d->stage_cap = 0;
-        const int64_t cap = kStageCand + std::max<int64_t>(2 * nc, 256);
-        if (hipHostMalloc(reinterpret_cast<void**>(&d->h_stage), sizeof(int32_t) * cap, hipHostMallocDefault) != hipSuccess)
-            return dpg_set_error(DPG_ERR_HIP, "hipHostMalloc(stage) failed");
-        d->stage_cap = cap;
-    }
-    if (d->d_stage.reserve((size_t)d->stage_cap) || d->d_cand_cnt.reserve((size_t)std::max<int64_t>(nc, 1)) ||
+    if (d->h_stage.cap < (size_t)(kStageCand + nc) && d->h_stage.reserve((size_t)(kStageCand + std::max<int64_t>(2 * nc, 256))))
+        return dpg_set_error(DPG_ERR_HIP, "hipHostMalloc(stage) failed");
+    if (d->d_stage.reserve(d->h_stage.cap) || d->d_cand_cnt.reserve((size_t)std::max<int64_t>(nc, 1)) ||
         d->d_acc.reserve((size_t)std::max<int64_t>(nc, 1)) || d->d_bins.reserve((size_t)(chain_n * bin_words)) ||
         d->d_inrange.reserve((size_t)chain_n) || d->d_commit.reserve((size_t)chain_n + 1) ||
         d->d_added.reserve((size_t)(chain_n * d->max_beams)) ||
         d->d_rmask.reserve((size_t)(std::max<int64_t>(nc, 1) * d->max_beams)) ||
         d->d_removed.reserve((size_t)(std::max<int64_t>(nc, 1) * d->max_beams)))
         return dpg_set_error(DPG_ERR_HIP, "hipMalloc(change scratch) failed");
-    DTRY(hipEventRecord(d->ev[0], s));
-    int32_t* hs = d->h_stage;   // the previous call ended with a stream synchronisation
+    DTRY(hipEventRecord(d->ev[0].e, s));
+    int32_t* hs = d->h_stage.p;   // the previous call ended with a stream synchronisation
     memcpy(hs, chain.data(), sizeof(int32_t) * chain_n);
     memcpy(hs + 16, slot.data(), sizeof(int32_t) * chain_n);
     if (!rast.empty()) memcpy(hs + 32, rast.data(), sizeof(int32_t) * rast.size());
@@ -1195,7 +1139,7 @@ int dpg_execute_dpg_chain(dpg_dpg* d, int64_t V, int64_t cur_len, const float* e
     // every active past node re-checks its active-sector fraction, removed points or not (dpg_node.cc:93-95)
     if (n_past > 0) deactivate_kernel<<<(unsigned)n_past, kT, 0, s>>>(ds);
     DTRY(hipGetLastError());
-    DTRY(hipEventRecord(d->ev[1], s));
+    DTRY(hipEventRecord(d->ev[1].e, s));
     return finish_call(d, V, chain_n, t0, st);
 }
 
@@ -1206,14 +1150,14 @@ namespace {
 // read back the counters and the node activity of one dpg_execute_dpg (one synchronisation)
 int finish_call(dpg_dpg* d, int64_t V, int64_t chain_n, double t0, dpg_change_stats* st) {
     hipStream_t s = d->s;
-    DTRY(hipMemcpyAsync(d->h_ctl, d->d_ctl.p, sizeof(Ctl), hipMemcpyDeviceToHost, s));
-    uint32_t* act = d->h_act;
+    DTRY(hipMemcpyAsync(d->h_ctl.p, d->d_ctl.p, sizeof(Ctl), hipMemcpyDeviceToHost, s));
+    uint32_t* act = d->h_act.p;
     DTRY(hipMemcpyAsync(act, d->d_active.p, sizeof(uint32_t) * V, hipMemcpyDeviceToHost, s));
-    int32_t* cm = d->h_commit;
+    int32_t* cm = d->h_commit.p;
     if (chain_n) DTRY(hipMemcpyAsync(cm, d->d_commit.p, sizeof(int32_t) * (chain_n + 1), hipMemcpyDeviceToHost, s));
     DTRY(hipStreamSynchronize(s));
     for (int64_t v = 0; v < V; ++v) d->active_h[(size_t)v] = act[(size_t)v] ? 1 : 0;
-    const Ctl& c = *d->h_ctl;
+    const Ctl& c = *d->h_ctl.p;
     if (c.oob) return dpg_set_error(DPG_ERR_STATE, "a pose-chain ray left the change-detection window");
     st->n_submap_nodes = c.n_acc;
     st->n_chain_cells = (int64_t)c.chain_cells;
@@ -1225,7 +1169,7 @@ int finish_call(dpg_dpg* d, int64_t V, int64_t chain_n, double t0, dpg_change_st
     st->n_samples = (int64_t)c.samples;
     for (int64_t k = 0; k < chain_n; ++k) st->n_committed += cm[(size_t)k] != 0;
     float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, d->ev[0], d->ev[1]);
+    (void)hipEventElapsedTime(&ms, d->ev[0].e, d->ev[1].e);
     st->ms_kernels = ms;
     st->ms_total = now_ms() - t0;
     return DPG_OK;
@@ -1358,8 +1302,8 @@ int dpg_occupancy_grid(dpg_dpg* d, int64_t V, const float* est, const dpg_grid_p
     std::vector<float> lidar((size_t)(2 * V));
     std::vector<int32_t> nodes;
     for (int64_t v = 0; v < V; ++v) {
-        lidar[(size_t)(2 * v)] = d->h_frames[8 * v];
-        lidar[(size_t)(2 * v + 1)] = d->h_frames[8 * v + 1];
+        lidar[(size_t)(2 * v)] = d->h_frames.p[8 * v];
+        lidar[(size_t)(2 * v + 1)] = d->h_frames.p[8 * v + 1];
         if (d->active_h[(size_t)v]) nodes.push_back((int32_t)v);
     }
     int32_t bx[4];
@@ -1387,7 +1331,7 @@ int dpg_occupancy_grid(dpg_dpg* d, int64_t V, const float* est, const dpg_grid_p
     int32_t* dh = d->d_occ_cnt.p;
     int32_t* dm = d->d_occ_cnt.p + pitch;
     DTRY(hipMemcpyAsync(d->d_occ_nodes.p, nodes.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
-    DTRY(hipEventRecord(d->ev[0], s));
+    DTRY(hipEventRecord(d->ev[0].e, s));
     DTRY(hipMemsetAsync(d->d_occ_cnt.p, 0, sizeof(int32_t) * 2 * pitch, s));
     DTRY(hipMemsetAsync(d->d_occ_ctl.p, 0, sizeof(OccCtl), s));
     occ_launch_variant(p.pad, ds, d->d_occ_nodes.p, n, d->max_beams, dh, dm, d->d_occ_ctl.p, s);
@@ -1396,7 +1340,7 @@ int dpg_occupancy_grid(dpg_dpg* d, int64_t V, const float* est, const dpg_grid_p
         occ_finalize_kernel<<<(unsigned)std::min<int64_t>((cells / 16 + kT) / kT, 2048), kT, 0, s>>>(dh, dm, d->d_occ_out.p, cells);
         DTRY(hipGetLastError());
     }
-    DTRY(hipEventRecord(d->ev[1], s));
+    DTRY(hipEventRecord(d->ev[1].e, s));
     // the outputs are staged so that a failure before this point leaves the caller's arrays untouched
     OccCtl c;
     DTRY(hipMemcpyAsync(&c, d->d_occ_ctl.p, sizeof(c), hipMemcpyDeviceToHost, s));
@@ -1412,7 +1356,7 @@ int dpg_occupancy_grid(dpg_dpg* d, int64_t V, const float* est, const dpg_grid_p
     info->n_direct = (int64_t)c.direct;
     info->n_flushed = (int64_t)c.flushed;
     float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, d->ev[0], d->ev[1]);
+    (void)hipEventElapsedTime(&ms, d->ev[0].e, d->ev[1].e);
     info->ms_kernels = ms;
     info->ms_total = now_ms() - t0;
     return DPG_OK;

@@ -26,7 +26,6 @@
 // factorization stay resident in HBM (tens of MB).
 
 #include <hip/hip_runtime.h>
-#include <time.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -35,10 +34,8 @@
 #include <algorithm>
 #include <vector>
 
-#include "dpg_chol.h"
 #include "dpg_chol_plan.h"
-#include "dpg_internal.h"
-#include "dpg_gn_pipe.h"
+#include "dpg_ctx.h"
 
 using namespace dpg_chol;   // the plan's records and the tile / panel constants (dpg_chol_plan.h)
 
@@ -2252,29 +2249,16 @@ __global__ __launch_bounds__(256) void chol_path_dot(const PathPair* __restrict_
     }
 }
 
-// device buffers are kept between rebuilds of the same solver (an incremental graph re-derives its
-// structures every update): a buffer is re-allocated only when it must grow (by 1.5x at least)
-template <typename T>
-int dreserve(T** d, size_t* cap, size_t n) {
-    n = std::max<size_t>(n, 1);
-    if (*d && n <= *cap) return DPG_OK;
-    if (*d) (void)hipFree(*d);
-    *d = nullptr;
-    const size_t nc = std::max(n, *cap + *cap / 2);
-    *cap = 0;
-    if (hipMalloc(reinterpret_cast<void**>(d), nc * sizeof(T)) != hipSuccess) return DPG_ERR_HIP;
-    *cap = nc;
-    return DPG_OK;
-}
-
 struct CholDev {
+    // (first among the resources, so destroyed last: the L11^-1 stream of the gated loop)
+    DevStream aux;
     dpg_chol_opts opts;   // the context's solver options at creation
     dpg_chol_sym sym;
     // the plan of `sym` (dpg_chol_plan.cpp): host arrays, sizes and launch parameters.  A plan and
     // its upload may run on different threads, one after the other; dpg_chol_plan_blocks fills its
     // H-block buckets beside the next analysis's derivation.
     CholPlan plan;
-    // the plan's arrays on the device (all in `arena`)
+    // the plan's arrays on the device: non-owning views into `arena`, set by chol_upload
     SnDev* sns = nullptr;
     OEnt* omap = nullptr;
     int32_t* child_list = nullptr;
@@ -2294,50 +2278,39 @@ struct CholDev {
     AsmChild* asm_child = nullptr;
     Task2* panel_tasks = nullptr;
     Task4* upd_tasks = nullptr;
-    // values
-    double* fronts = nullptr;
-    double* acc = nullptr;
-    double* ysol = nullptr;
-    double* xsol = nullptr;
-    int32_t* status = nullptr;
-    double* dinv = nullptr;            // inverted diagonal blocks of the solves ([3n][kSB])
-    double* linv = nullptr;            // L11^-1 of the large fronts (SnDev.inv offsets)
-    size_t c_linv = 0;
-    int32_t* sync = nullptr;           // plan.sync_bytes of counters and flags, zeroed per solve (SyncWords)
+    // values.  The buffers are kept between rebuilds of the same solver (an incremental graph
+    // re-derives its structures every update): re-allocated only when one must grow, by 1.5x at least
+    DevBuf<double> fronts, acc, ysol, xsol;
+    DevBuf<int32_t> status;
+    DevBuf<double> dinv;               // inverted diagonal blocks of the solves ([3n][kSB])
+    DevBuf<double> linv;               // L11^-1 of the large fronts (SnDev.inv offsets)
+    DevBuf<int32_t> sync;              // plan.sync_bytes of counters and flags, zeroed per solve (SyncWords)
     // L11^-1 (chol_inv_l11): valid for the last factorization (inv_valid: computed by an ungated
     // solve); the gated loop computes it on `aux` beside each refactoring iteration's backward solve
     // and its chord iterations wait for it (ev_inv of the previous iteration)
     bool inv_valid = false;
     bool keep_inv = false;   // ungated solves compute L11^-1 after their backward solve (for dpg_chol_resolve)
-    hipStream_t aux = nullptr;
-    hipEvent_t ev_fac = nullptr, ev_inv[2] = {nullptr, nullptr};
+    DevEvent ev_fac, ev_inv[2];
     int inv_par = 0;
-    // capacities (elements) of the device buffers above, for rebuilds
-    size_t c_fronts = 0, c_acc = 0, c_ysol = 0, c_xsol = 0, c_status = 0, c_sync = 0, c_dinv = 0;
     double t_build[2] = {0, 0};   // last chol_build: host structures, uploads (ms)
-    char* stage = nullptr;        // pinned staging buffer of the uploads
-    size_t c_stage = 0;
-    char* arena = nullptr;        // device: every structure array above (sns .. upd_tasks), one copy
-    size_t c_arena = 0;
+    PinBuf<char> stage;           // pinned staging buffer of the uploads
+    DevBuf<char> arena;           // device: every structure array above (sns .. upd_tasks), one copy
     // partial refactorization (dpg_chol_track_factor): `fac_sym` is the analysis the values in
     // `fronts` were factored under (valid while fac_valid and fronts == fac_ptr), fac_G its team
     // sizes; sym_is_fac: the current analysis is that one (it moves to fac_sym with the next plan)
     bool track = false, fac_valid = false, sym_is_fac = false, fac_db = false;
     double* fac_ptr = nullptr;         // fronts, y and the pending updates of that factorization
-    double* fac_ysol = nullptr;
+    double* fac_ysol = nullptr;        // (identities to compare with, not owned)
     double* fac_acc = nullptr;
     dpg_chol_sym fac_sym;
     std::vector<int32_t> fac_G;   // (the current analysis's: plan.cur_G)
     std::vector<uint8_t> h_keep;
     std::vector<int32_t> h_old;
     std::vector<int64_t> h_runs;
-    double* scratch = nullptr;    // the moved fronts between the gather and the scatter
-    size_t c_scratch = 0;
-    char* pstage = nullptr;       // pinned: keep flags + runs, one copy up
-    size_t c_pstage = 0;
-    char* dpart = nullptr;
-    size_t c_dpart = 0;
-    hipEvent_t pev = nullptr;     // after that copy (the staging buffer's next rewrite waits for it)
+    DevBuf<double> scratch;       // the moved fronts between the gather and the scatter
+    PinBuf<char> pstage;          // pinned: keep flags + runs, one copy up
+    DevBuf<char> dpart;
+    DevEvent pev;                 // after that copy (the staging buffer's next rewrite waits for it)
     bool pev_set = false;
     int64_t pstats[4] = {0, 0, 0, 0};   // last solve: fronts refactored, kept, doubles moved, host ns of the pick
     // selected inverse (dpg_chol_selinv): nothing here is allocated or built before the first
@@ -2346,24 +2319,20 @@ struct CholDev {
     // uploaded as number build_gen (sel_gen: the one they were built for).
     bool has_factor = false;      // `fronts` holds a factorization under the current analysis
     int64_t build_gen = 0, sel_gen = -1;
-    double* sel = nullptr;
-    double* sel_work = nullptr;
-    double* sel_out = nullptr;
-    char* sel_lists = nullptr;    // [int64 woff[ns] | int32 list[ns]]
-    SelPick* sel_picks = nullptr;
-    size_t c_sel = 0, c_sel_work = 0, c_sel_out = 0, c_sel_lists = 0, c_sel_picks = 0;
+    DevBuf<double> sel, sel_work, sel_out;
+    DevBuf<char> sel_lists;       // [int64 woff[ns] | int32 list[ns]]
+    DevBuf<SelPick> sel_picks;
     std::vector<size_t> sel_lds;  // per level: dynamic LDS bytes of its launch
     std::vector<SelPick> h_picks;
-    std::vector<hipEvent_t> sel_ev;
+    std::vector<DevEvent> sel_ev;
     // joint marginals (dpg_chol_joint): its own plan and buffers, allocated by the first request and
     // regrown only when a request needs more; nothing above is written
     JointPlan jplan;
-    double* jt_w = nullptr;       // the compact W buffer (the queries' slices)
-    double* jt_work = nullptr;    // the path solve's vectors when they do not fit LDS
-    double* jt_out = nullptr;
-    char* jt_lists = nullptr;     // [PathPair pairs | PathQuery queries]
-    size_t c_jt_w = 0, c_jt_work = 0, c_jt_out = 0, c_jt_lists = 0;
-    hipEvent_t jt_ev[3] = {nullptr, nullptr, nullptr};
+    DevBuf<double> jt_w;          // the compact W buffer (the queries' slices)
+    DevBuf<double> jt_work;       // the path solve's vectors when they do not fit LDS
+    DevBuf<double> jt_out;
+    DevBuf<char> jt_lists;        // [PathPair pairs | PathQuery queries]
+    DevEvent jt_ev[3];
 };
 
 // a new analysis in; *S gets back one whose buffers the caller reuses.  With tracking, the analysis
@@ -2383,22 +2352,7 @@ void take_sym(CholDev* c, dpg_chol_sym* S) {
 extern "C" void dpg_chol_destroy(void* h) {
     CholDev* c = reinterpret_cast<CholDev*>(h);
     if (!c) return;
-    // (the structure arrays live in c->arena)
-    if (c->aux) (void)hipStreamSynchronize(c->aux);
-    void* ptrs[] = {c->arena, c->fronts, c->acc, c->ysol, c->xsol, c->status, c->sync, c->dinv, c->linv, c->scratch, c->dpart,
-                    c->sel, c->sel_work, c->sel_out, c->sel_lists, c->sel_picks, c->jt_w, c->jt_work, c->jt_out, c->jt_lists};
-    for (hipEvent_t e : c->sel_ev) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->jt_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (c->pev) (void)hipEventDestroy(c->pev);
-    if (c->pstage) (void)hipHostFree(c->pstage);
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    if (c->stage) (void)hipHostFree(c->stage);
-    if (c->ev_fac) (void)hipEventDestroy(c->ev_fac);
-    for (hipEvent_t e : c->ev_inv)
-        if (e) (void)hipEventDestroy(e);
-    if (c->aux) (void)hipStreamDestroy(c->aux);
+    if (c->aux.s) (void)hipStreamSynchronize(c->aux.s);
     delete c;
 }
 
@@ -2435,12 +2389,6 @@ int dpg_chol_create_sym(void** h, int64_t n, const int32_t* pair_lo, const int32
 }
 
 namespace {
-double wall_ms() {
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (double)ts.tv_sec * 1e3 + (double)ts.tv_nsec * 1e-6;
-}
-
 // The structure arrays are packed into one pinned staging buffer and go up in ONE asynchronous
 // copy into one device arena (the pointers of c point into it); one synchronisation at the end.
 int chol_upload(CholDev* c) {
@@ -2480,42 +2428,27 @@ int chol_upload(CholDev* c) {
     }
     size_t total = 0;
     for (int i = 0; i < np; ++i) total += al(std::max<size_t>(pieces[i].bytes, 1));
-    if (total > c->c_stage) {
-        if (c->stage) (void)hipHostFree(c->stage);
-        c->stage = nullptr;
-        const size_t want = std::max(total, c->c_stage + c->c_stage / 2);
-        c->c_stage = 0;
-        if (hipHostMalloc(reinterpret_cast<void**>(&c->stage), want) != hipSuccess) return DPG_ERR_HIP;
-        c->c_stage = want;
-    }
-    if (total > c->c_arena) {
-        if (c->arena) (void)hipFree(c->arena);
-        c->arena = nullptr;
-        const size_t want = std::max(total, c->c_arena + c->c_arena / 2);
-        c->c_arena = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&c->arena), want) != hipSuccess) return DPG_ERR_HIP;
-        c->c_arena = want;
-    }
+    if (c->stage.reserve_amortised(total) || c->arena.reserve_amortised(total)) return DPG_ERR_HIP;
     size_t off = 0;
     for (int i = 0; i < np; ++i) {
-        if (pieces[i].bytes) memcpy(c->stage + off, pieces[i].h, pieces[i].bytes);
-        *pieces[i].d = c->arena + off;
+        if (pieces[i].bytes) memcpy(c->stage.p + off, pieces[i].h, pieces[i].bytes);
+        *pieces[i].d = c->arena.p + off;
         off += al(std::max<size_t>(pieces[i].bytes, 1));
     }
-    int rc = hipMemcpyAsync(c->arena, c->stage, total, hipMemcpyHostToDevice, nullptr) != hipSuccess;
+    int rc = hipMemcpyAsync(c->arena.p, c->stage.p, total, hipMemcpyHostToDevice, nullptr) != hipSuccess;
     // a re-allocated front, y or pending-update buffer has lost the tracked factorization (a new
     // allocation may come back at the old address: the capacities tell)
-    const size_t cap0[3] = {c->c_fronts, c->c_acc, c->c_ysol};
-    rc |= dreserve(&c->sync, &c->c_sync, H.sync_bytes / sizeof(int32_t));
-    rc |= dreserve(&c->fronts, &c->c_fronts, (size_t)S.front_off[(size_t)S.ns]);
-    rc |= dreserve(&c->acc, &c->c_acc, (size_t)H.acc_total);
-    rc |= dreserve(&c->ysol, &c->c_ysol, (size_t)(3 * n));
-    if (rc || cap0[0] != c->c_fronts || cap0[1] != c->c_acc || cap0[2] != c->c_ysol) c->fac_valid = false;
-    rc |= dreserve(&c->xsol, &c->c_xsol, (size_t)(3 * n));
-    rc |= dreserve(&c->status, &c->c_status, 1);
-    rc |= dreserve(&c->dinv, &c->c_dinv, (size_t)(3 * n) * kSB);
-    rc |= dreserve(&c->linv, &c->c_linv, (size_t)std::max<int64_t>(H.linv_total, 1));
-    if (!rc) rc |= hipMemsetAsync(c->status, 0, sizeof(int32_t), nullptr) != hipSuccess;
+    const size_t cap0[3] = {c->fronts.cap, c->acc.cap, c->ysol.cap};
+    rc |= c->sync.reserve_amortised(H.sync_bytes / sizeof(int32_t));
+    rc |= c->fronts.reserve_amortised((size_t)S.front_off[(size_t)S.ns]);
+    rc |= c->acc.reserve_amortised((size_t)H.acc_total);
+    rc |= c->ysol.reserve_amortised((size_t)(3 * n));
+    if (rc || cap0[0] != c->fronts.cap || cap0[1] != c->acc.cap || cap0[2] != c->ysol.cap) c->fac_valid = false;
+    rc |= c->xsol.reserve_amortised((size_t)(3 * n));
+    rc |= c->status.reserve_amortised(1);
+    rc |= c->dinv.reserve_amortised((size_t)(3 * n) * kSB);
+    rc |= c->linv.reserve_amortised((size_t)std::max<int64_t>(H.linv_total, 1));
+    if (!rc) rc |= hipMemsetAsync(c->status.p, 0, sizeof(int32_t), nullptr) != hipSuccess;
     // the staging buffer is reused by the next build: wait for the copy (always, even after an error)
     rc |= hipStreamSynchronize(nullptr) != hipSuccess;
     return rc ? DPG_ERR_HIP : DPG_OK;
@@ -2524,15 +2457,15 @@ int chol_upload(CholDev* c) {
 // (a plan and its upload may be split: dpg_chol_create_sym_plan / _upload, possibly on two threads
 // one after the other)
 int chol_build_plan(CholDev* c, int64_t n, const int32_t* pair_lo, const int32_t* pair_hi, int64_t n_pairs) {
-    const double t_b0 = wall_ms();
+    const double t_b0 = now_ms();
     const int rc = dpg_chol_plan_build(c->plan, c->sym, c->opts, c->track, n, pair_lo, pair_hi, n_pairs);
-    c->t_build[0] = wall_ms() - t_b0;
+    c->t_build[0] = now_ms() - t_b0;
     return rc;
 }
 int chol_build_upload(CholDev* c) {
-    const double t_b1 = wall_ms();
+    const double t_b1 = now_ms();
     const int rc = chol_upload(c);
-    c->t_build[1] = wall_ms() - t_b1;
+    c->t_build[1] = now_ms() - t_b1;
     return rc;
 }
 int chol_build(CholDev* c, int64_t n, const int32_t* pair_lo, const int32_t* pair_hi, int64_t n_pairs) {
@@ -2607,16 +2540,16 @@ void dpg_chol_build_times(void* h, double out[2]) {
 // fused factorization + forward solve of hb's system (its right-hand side follows its blocks)
 static void launch_factor(CholDev* c, hipStream_t st, const double* hb, const int32_t* gate, const uint8_t* keep) {
     const CholPlan& P = c->plan;
-    hipLaunchKernelGGL(chol_factor_dag, dim3((unsigned)P.n_tickets), dim3(kFT), P.lds_fused, st, c->order_fac, c->sync,
-                       c->status, c->sns, c->omap, c->relmap, c->child_list, c->ftasks, c->fchild, hb, hb + 9 * P.nnzb_upper,
-                       c->perm, c->fronts, c->ysol, c->acc, c->sym.ns, P.fused_db ? 1 : 0, gate, keep);
+    hipLaunchKernelGGL(chol_factor_dag, dim3((unsigned)P.n_tickets), dim3(kFT), P.lds_fused, st, c->order_fac, c->sync.p,
+                       c->status.p, c->sns, c->omap, c->relmap, c->child_list, c->ftasks, c->fchild, hb, hb + 9 * P.nnzb_upper,
+                       c->perm, c->fronts.p, c->ysol.p, c->acc.p, c->sym.ns, P.fused_db ? 1 : 0, gate, keep);
 }
 
 static void launch_forward(CholDev* c, hipStream_t st, const double* hb, const double* di, const int32_t* gate,
                            const double* li) {
     const CholPlan& P = c->plan;
-    hipLaunchKernelGGL(chol_forward_dag, dim3(c->sym.ns), dim3(kT), P.lds_solve_max, st, c->order_fwd, c->sync, c->status,
-                       c->sns, c->child_list, c->relmap, c->fronts, hb + 9 * P.nnzb_upper, c->perm, c->ysol, c->acc,
+    hipLaunchKernelGGL(chol_forward_dag, dim3(c->sym.ns), dim3(kT), P.lds_solve_max, st, c->order_fwd, c->sync.p, c->status.p,
+                       c->sns, c->child_list, c->relmap, c->fronts.p, hb + 9 * P.nnzb_upper, c->perm, c->ysol.p, c->acc.p,
                        P.solve_stage, di, gate, li);
 }
 
@@ -2624,8 +2557,8 @@ static void launch_backward(CholDev* c, hipStream_t st, const double* di, const 
                             const double* li) {
     const CholPlan& P = c->plan;
     const int32_t ns = c->sym.ns;
-    hipLaunchKernelGGL(chol_backward_dag, dim3(ns), dim3(kT), P.lds_solve_max, st, c->order_bwd, c->sync + 1 + 2 * ns,
-                       c->status, c->sns, c->rows, c->segs, c->fronts, c->ysol, c->xsol, P.solve_stage, P.solve_maxseg, di, gate,
+    hipLaunchKernelGGL(chol_backward_dag, dim3(ns), dim3(kT), P.lds_solve_max, st, c->order_bwd, c->sync.p + 1 + 2 * ns,
+                       c->status.p, c->sns, c->rows, c->segs, c->fronts.p, c->ysol.p, c->xsol.p, P.solve_stage, P.solve_maxseg, di, gate,
                        X ? c->perm : nullptr, X, max_out, li);
 }
 
@@ -2634,8 +2567,8 @@ static void launch_backward(CholDev* c, hipStream_t st, const double* di, const 
 static const double* launch_inv_diag(CholDev* c, hipStream_t st) {
     const CholPlan& P = c->plan;
     if (P.use_dinv && P.n_dblocks > 0)
-        hipLaunchKernelGGL(chol_inv_diag, dim3((unsigned)P.n_dblocks), dim3(64), 0, st, c->dblocks, c->sns, c->fronts, c->dinv);
-    return P.use_dinv ? c->dinv : nullptr;
+        hipLaunchKernelGGL(chol_inv_diag, dim3((unsigned)P.n_dblocks), dim3(64), 0, st, c->dblocks, c->sns, c->fronts.p, c->dinv.p);
+    return P.use_dinv ? c->dinv.p : nullptr;
 }
 
 // L11^-1 of the large fronts from the fronts just factored (gate: the pipelined loop's, refactoring
@@ -2644,7 +2577,7 @@ static void launch_inv(CholDev* c, hipStream_t st, const int32_t* gate) {
     const CholPlan& P = c->plan;
     if (P.n_inv_tasks > 0)
         hipLaunchKernelGGL(chol_inv_l11, dim3((unsigned)P.n_inv_tasks), dim3(kInvThreads), P.lds_inv, st, c->inv_tasks, c->sns,
-                           c->fronts, c->linv, gate);
+                           c->fronts.p, c->linv.p, gate);
 }
 
 // the level-synchronous factorization: per level, assembly tiles, then panel + update steps
@@ -2652,14 +2585,14 @@ static void launch_levels(CholDev* c, hipStream_t st, const double* hb) {
     int pid = 0;
     for (const CholPlan::Level& L : c->plan.levels) {
         hipLaunchKernelGGL(chol_assemble, dim3(L.asm_cnt), dim3(kT), L.lds_asm, st, c->asm_tasks + L.asm_off,
-                           c->asm_child, c->sns, c->omap, hb, c->relmap, c->fronts, pid++);
+                           c->asm_child, c->sns, c->omap, hb, c->relmap, c->fronts.p, pid++);
         for (const CholPlan::Step& p : L.steps) {
             const Task2* pt = c->panel_tasks + p.panel_off;
-            if (p.rpt == 1) hipLaunchKernelGGL(chol_panel<kT>, dim3(p.panel_cnt), dim3(kT), 0, st, pt, c->sns, c->fronts, c->status, pid++);
-            else if (p.rpt == 2) hipLaunchKernelGGL(chol_panel<2 * kT>, dim3(p.panel_cnt), dim3(2 * kT), 0, st, pt, c->sns, c->fronts, c->status, pid++);
-            else hipLaunchKernelGGL(chol_panel<4 * kT>, dim3(p.panel_cnt), dim3(4 * kT), 0, st, pt, c->sns, c->fronts, c->status, pid++);
+            if (p.rpt == 1) hipLaunchKernelGGL(chol_panel<kT>, dim3(p.panel_cnt), dim3(kT), 0, st, pt, c->sns, c->fronts.p, c->status.p, pid++);
+            else if (p.rpt == 2) hipLaunchKernelGGL(chol_panel<2 * kT>, dim3(p.panel_cnt), dim3(2 * kT), 0, st, pt, c->sns, c->fronts.p, c->status.p, pid++);
+            else hipLaunchKernelGGL(chol_panel<4 * kT>, dim3(p.panel_cnt), dim3(4 * kT), 0, st, pt, c->sns, c->fronts.p, c->status.p, pid++);
             if (p.upd_cnt > 0)
-                hipLaunchKernelGGL(chol_update, dim3(p.upd_cnt), dim3(kT), 0, st, c->upd_tasks + p.upd_off, c->sns, c->fronts, pid++);
+                hipLaunchKernelGGL(chol_update, dim3(p.upd_cnt), dim3(kT), 0, st, c->upd_tasks + p.upd_off, c->sns, c->fronts.p, pid++);
         }
     }
 }
@@ -2673,9 +2606,9 @@ static void note_factored(CholDev* c, int64_t refactored, int64_t kept, int64_t 
     c->has_factor = true;
     if (!c->track) return;
     c->fac_valid = true;
-    c->fac_ptr = c->fronts;
-    c->fac_ysol = c->ysol;
-    c->fac_acc = c->acc;
+    c->fac_ptr = c->fronts.p;
+    c->fac_ysol = c->ysol.p;
+    c->fac_acc = c->acc.p;
     c->sym_is_fac = true;
     c->fac_db = c->plan.fused_db;
 }
@@ -2685,13 +2618,13 @@ extern "C" int dpg_chol_solve(void* h, const double* hb, void* stream) {
     const CholPlan& P = c->plan;
     note_factored(c, c->sym.ns, 0, 0);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (hipMemsetAsync(c->status, 0, sizeof(int32_t), st) != hipSuccess) return DPG_ERR_HIP;
+    if (hipMemsetAsync(c->status.p, 0, sizeof(int32_t), st) != hipSuccess) return DPG_ERR_HIP;
     if (P.fused) {
-        if (hipMemsetAsync(c->sync, 0, P.sync_bytes, st) != hipSuccess) return DPG_ERR_HIP;
+        if (hipMemsetAsync(c->sync.p, 0, P.sync_bytes, st) != hipSuccess) return DPG_ERR_HIP;
         launch_factor(c, st, hb, nullptr, nullptr);
     } else {
         launch_levels(c, st, hb);
-        if (hipMemsetAsync(c->sync, 0, P.sync_bytes, st) != hipSuccess) return DPG_ERR_HIP;
+        if (hipMemsetAsync(c->sync.p, 0, P.sync_bytes, st) != hipSuccess) return DPG_ERR_HIP;
     }
     const double* di = launch_inv_diag(c, st);
     if (!P.fused) launch_forward(c, st, hb, di, nullptr, nullptr);
@@ -2744,13 +2677,13 @@ extern "C" int dpg_chol_solve_partial(void* h, const double* hb, const int32_t* 
     const dpg_chol_sym& S = c->sym;
     const dpg_chol_sym& O = c->fac_sym;
     const CholPlan& P = c->plan;
-    const bool usable = c->track && c->fac_valid && !c->sym_is_fac && c->fac_ptr == c->fronts &&
-                        c->fac_ysol == c->ysol && c->fac_acc == c->acc && P.fused &&
+    const bool usable = c->track && c->fac_valid && !c->sym_is_fac && c->fac_ptr == c->fronts.p &&
+                        c->fac_ysol == c->ysol.p && c->fac_acc == c->acc.p && P.fused &&
                         !(P.use_dinv && P.n_dblocks > 0) && c->fac_db == P.fused_db && O.ns > 0 && O.n <= S.n &&
                         (int64_t)c->fac_G.size() == (int64_t)O.ns && (int64_t)P.cur_G.size() == (int64_t)S.ns &&
                         std::equal(O.perm.begin(), O.perm.end(), S.perm.begin());
     if (!usable) return dpg_chol_solve(h, hb, stream);
-    const double t_pick = wall_ms();
+    const double t_pick = now_ms();
     const int32_t ns = S.ns;
     std::vector<uint8_t>& keep = c->h_keep;
     std::vector<int32_t>& old = c->h_old;
@@ -2827,19 +2760,12 @@ extern "C" int dpg_chol_solve_partial(void* h, const double* hb, const int32_t* 
     const size_t keep_bytes = ((size_t)ns + 15) & ~size_t(15);
     const size_t run_bytes = sizeof(int64_t) * 4 * (size_t)nruns;
     const size_t bytes = keep_bytes + 2 * run_bytes;
-    if (c->pev_set && hipEventSynchronize(c->pev) != hipSuccess) return DPG_ERR_HIP;
-    if (bytes > c->c_pstage) {
-        if (c->pstage) (void)hipHostFree(c->pstage);
-        c->pstage = nullptr;
-        const size_t want = std::max(bytes, c->c_pstage + c->c_pstage / 2);
-        c->c_pstage = 0;
-        if (hipHostMalloc(reinterpret_cast<void**>(&c->pstage), want) != hipSuccess) return DPG_ERR_HIP;
-        c->c_pstage = want;
-    }
-    if (dreserve(&c->dpart, &c->c_dpart, bytes) || (moved > 0 && dreserve(&c->scratch, &c->c_scratch, (size_t)moved)))
+    if (c->pev_set && hipEventSynchronize(c->pev.e) != hipSuccess) return DPG_ERR_HIP;
+    if (c->pstage.reserve_amortised(bytes) || c->dpart.reserve_amortised(bytes) ||
+        (moved > 0 && c->scratch.reserve_amortised((size_t)moved)))
         return DPG_ERR_HIP;
-    memcpy(c->pstage, keep.data(), (size_t)ns);
-    int64_t* gat = reinterpret_cast<int64_t*>(c->pstage + keep_bytes);
+    memcpy(c->pstage.p, keep.data(), (size_t)ns);
+    int64_t* gat = reinterpret_cast<int64_t*>(c->pstage.p + keep_bytes);
     int64_t* sca = gat + 4 * nruns;
     for (int64_t r = 0, off = 0; r < nruns; ++r) {
         const int64_t* q = runs.data() + 4 * r;
@@ -2848,27 +2774,27 @@ extern "C" int dpg_chol_solve_partial(void* h, const double* hb, const int32_t* 
         std::copy(s4, s4 + 4, sca + 4 * r);
         off += q[2];
     }
-    if (!c->pev && hipEventCreateWithFlags(&c->pev, hipEventDisableTiming) != hipSuccess) return DPG_ERR_HIP;
-    if (hipMemcpyAsync(c->dpart, c->pstage, bytes, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipEventRecord(c->pev, st) != hipSuccess)
+    if (c->pev.ensure(hipEventDisableTiming)) return DPG_ERR_HIP;
+    if (hipMemcpyAsync(c->dpart.p, c->pstage.p, bytes, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipEventRecord(c->pev.e, st) != hipSuccess)
         return DPG_ERR_HIP;
     c->pev_set = true;
-    const uint8_t* keep_dev = reinterpret_cast<const uint8_t*>(c->dpart);
-    const int64_t* gat_dev = reinterpret_cast<const int64_t*>(c->dpart + keep_bytes);
+    const uint8_t* keep_dev = reinterpret_cast<const uint8_t*>(c->dpart.p);
+    const int64_t* gat_dev = reinterpret_cast<const int64_t*>(c->dpart.p + keep_bytes);
     const int64_t* sca_dev = gat_dev + 4 * nruns;
     if (nruns > 0) {
         const unsigned gx = (unsigned)std::min<int64_t>(64, std::max<int64_t>(1, (max_run + 2047) / 2048));
-        hipLaunchKernelGGL(chol_copy_runs, dim3(gx, (unsigned)nruns), dim3(256), 0, st, c->fronts, c->acc, c->scratch,
-                           c->scratch, gat_dev);
-        hipLaunchKernelGGL(chol_copy_runs, dim3(gx, (unsigned)nruns), dim3(256), 0, st, c->scratch, c->scratch, c->fronts,
-                           c->acc, sca_dev);
+        hipLaunchKernelGGL(chol_copy_runs, dim3(gx, (unsigned)nruns), dim3(256), 0, st, c->fronts.p, c->acc.p, c->scratch.p,
+                           c->scratch.p, gat_dev);
+        hipLaunchKernelGGL(chol_copy_runs, dim3(gx, (unsigned)nruns), dim3(256), 0, st, c->scratch.p, c->scratch.p, c->fronts.p,
+                           c->acc.p, sca_dev);
     }
-    if (hipMemsetAsync(c->status, 0, sizeof(int32_t), st) != hipSuccess ||
-        hipMemsetAsync(c->sync, 0, P.sync_bytes, st) != hipSuccess)
+    if (hipMemsetAsync(c->status.p, 0, sizeof(int32_t), st) != hipSuccess ||
+        hipMemsetAsync(c->sync.p, 0, P.sync_bytes, st) != hipSuccess)
         return DPG_ERR_HIP;
     launch_factor(c, st, hb, nullptr, keep_dev);
     launch_backward(c, st, nullptr, nullptr, nullptr, nullptr, nullptr);
-    note_factored(c, ns - kept, kept, moved, (int64_t)((wall_ms() - t_pick) * 1e6));
+    note_factored(c, ns - kept, kept, moved, (int64_t)((now_ms() - t_pick) * 1e6));
     c->inv_valid = false;
     return hipGetLastError() == hipSuccess ? DPG_OK : DPG_ERR_HIP;
 }
@@ -2877,9 +2803,9 @@ extern "C" int dpg_chol_solve_partial(void* h, const double* hb, const int32_t* 
 extern "C" int dpg_chol_resolve(void* h, const double* hb, void* stream) {
     CholDev* c = reinterpret_cast<CholDev*>(h);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (hipMemsetAsync(c->sync, 0, c->plan.sync_bytes, st) != hipSuccess) return DPG_ERR_HIP;
-    const double* di = c->plan.use_dinv ? c->dinv : nullptr;   // inverted by the factorization's dpg_chol_solve
-    const double* li = c->inv_valid ? c->linv : nullptr;
+    if (hipMemsetAsync(c->sync.p, 0, c->plan.sync_bytes, st) != hipSuccess) return DPG_ERR_HIP;
+    const double* di = c->plan.use_dinv ? c->dinv.p : nullptr;   // inverted by the factorization's dpg_chol_solve
+    const double* li = c->inv_valid ? c->linv.p : nullptr;
     launch_forward(c, st, hb, di, nullptr, li);
     launch_backward(c, st, di, nullptr, nullptr, nullptr, li);
     return hipGetLastError() == hipSuccess ? DPG_OK : DPG_ERR_HIP;
@@ -2895,7 +2821,7 @@ extern "C" int dpg_chol_gated_ok(void* h) {
 
 extern "C" void dpg_chol_sync_dev(void* h, int32_t** sync, int64_t* n_words) {
     CholDev* c = reinterpret_cast<CholDev*>(h);
-    *sync = c->sync;
+    *sync = c->sync.p;
     *n_words = (int64_t)(c->plan.sync_bytes / sizeof(int32_t));
 }
 
@@ -2907,31 +2833,30 @@ extern "C" int dpg_chol_solve_gated(void* h, const double* hb, const int32_t* ga
     c->fac_valid = false;   // (a Gauss-Newton loop's refactorizations are not tracked)
     c->has_factor = true;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (!prezeroed && (hipMemsetAsync(c->status, 0, sizeof(int32_t), st) != hipSuccess ||
-                       hipMemsetAsync(c->sync, 0, c->plan.sync_bytes, st) != hipSuccess))
+    if (!prezeroed && (hipMemsetAsync(c->status.p, 0, sizeof(int32_t), st) != hipSuccess ||
+                       hipMemsetAsync(c->sync.p, 0, c->plan.sync_bytes, st) != hipSuccess))
         return DPG_ERR_HIP;
     const bool inv = c->plan.n_inv_tasks > 0;
     if (inv) {   // this iteration's solves come after the previous iteration's inverse
-        if (!c->aux) {
-            if (hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking) != hipSuccess ||
-                hipEventCreateWithFlags(&c->ev_fac, hipEventDisableTiming) != hipSuccess ||
-                hipEventCreateWithFlags(&c->ev_inv[0], hipEventDisableTiming) != hipSuccess ||
-                hipEventCreateWithFlags(&c->ev_inv[1], hipEventDisableTiming) != hipSuccess ||
-                hipEventRecord(c->ev_inv[0], c->aux) != hipSuccess || hipEventRecord(c->ev_inv[1], c->aux) != hipSuccess)
+        if (!c->aux.s) {
+            if (hipStreamCreateWithFlags(&c->aux.s, hipStreamNonBlocking) != hipSuccess ||
+                c->ev_fac.ensure(hipEventDisableTiming) || c->ev_inv[0].ensure(hipEventDisableTiming) ||
+                c->ev_inv[1].ensure(hipEventDisableTiming) || hipEventRecord(c->ev_inv[0].e, c->aux.s) != hipSuccess ||
+                hipEventRecord(c->ev_inv[1].e, c->aux.s) != hipSuccess)
                 return DPG_ERR_HIP;
         }
-        if (hipStreamWaitEvent(st, c->ev_inv[c->inv_par ^ 1], 0) != hipSuccess) return DPG_ERR_HIP;
+        if (hipStreamWaitEvent(st, c->ev_inv[c->inv_par ^ 1].e, 0) != hipSuccess) return DPG_ERR_HIP;
     }
     launch_factor(c, st, hb, gate, nullptr);
     if (inv) {   // L11^-1 of a refactoring iteration beside its backward solve (which does not use it)
-        if (hipEventRecord(c->ev_fac, st) != hipSuccess || hipStreamWaitEvent(c->aux, c->ev_fac, 0) != hipSuccess)
+        if (hipEventRecord(c->ev_fac.e, st) != hipSuccess || hipStreamWaitEvent(c->aux.s, c->ev_fac.e, 0) != hipSuccess)
             return DPG_ERR_HIP;
-        launch_inv(c, c->aux, gate);
-        if (hipEventRecord(c->ev_inv[c->inv_par], c->aux) != hipSuccess) return DPG_ERR_HIP;
+        launch_inv(c, c->aux.s, gate);
+        if (hipEventRecord(c->ev_inv[c->inv_par].e, c->aux.s) != hipSuccess) return DPG_ERR_HIP;
         c->inv_par ^= 1;
     }
-    launch_forward(c, st, hb, nullptr, gate, c->linv);
-    launch_backward(c, st, nullptr, gate, X, max_out, c->linv);
+    launch_forward(c, st, hb, nullptr, gate, c->linv.p);
+    launch_backward(c, st, nullptr, gate, X, max_out, c->linv.p);
     return hipGetLastError() == hipSuccess ? DPG_OK : DPG_ERR_HIP;
 }
 
@@ -2945,14 +2870,14 @@ extern "C" void dpg_chol_keep_inverse(void* h, int on) {
 // this iteration's inverse (normally long finished: it ran beside the backward solve and assembly)
 extern "C" int dpg_chol_join_aux(void* h, void* stream) {
     CholDev* c = reinterpret_cast<CholDev*>(h);
-    if (!c || !c->aux) return DPG_OK;
-    return hipStreamWaitEvent(reinterpret_cast<hipStream_t>(stream), c->ev_inv[c->inv_par ^ 1], 0) == hipSuccess ? DPG_OK
+    if (!c || !c->aux.s) return DPG_OK;
+    return hipStreamWaitEvent(reinterpret_cast<hipStream_t>(stream), c->ev_inv[c->inv_par ^ 1].e, 0) == hipSuccess ? DPG_OK
                                                                                                        : DPG_ERR_HIP;
 }
 
 extern "C" const int32_t* dpg_chol_pos_dev(void* h) { return reinterpret_cast<CholDev*>(h)->pos; }
-extern "C" const double* dpg_chol_x_dev(void* h) { return reinterpret_cast<CholDev*>(h)->xsol; }
-extern "C" const int32_t* dpg_chol_status_dev(void* h) { return reinterpret_cast<CholDev*>(h)->status; }
+extern "C" const double* dpg_chol_x_dev(void* h) { return reinterpret_cast<CholDev*>(h)->xsol.p; }
+extern "C" const int32_t* dpg_chol_status_dev(void* h) { return reinterpret_cast<CholDev*>(h)->status.p; }
 extern "C" void dpg_chol_stats(void* h, double out[6]) {
     const dpg_chol_sym& S = reinterpret_cast<CholDev*>(h)->sym;
     out[0] = S.ns;
@@ -2969,7 +2894,7 @@ namespace {
 int selinv_prepare(CholDev* c, hipStream_t st) {
     const dpg_chol_sym& S = c->sym;
     const size_t total = (size_t)S.front_off[(size_t)S.ns];
-    if (c->sel_gen == c->build_gen && c->sel && total <= c->c_sel) return DPG_OK;
+    if (c->sel_gen == c->build_gen && c->sel.p && total <= c->sel.cap) return DPG_OK;
     // (an earlier request's kernels may still read what is rebuilt here)
     if (hipStreamSynchronize(st) != hipSuccess) return DPG_ERR_HIP;
     const int32_t ns = S.ns;
@@ -2990,11 +2915,10 @@ int selinv_prepare(CholDev* c, hipStream_t st) {
         }
     }
     const size_t lb = sizeof(int64_t) * (size_t)ns + sizeof(int32_t) * (size_t)ns;
-    if (dreserve(&c->sel, &c->c_sel, total) || dreserve(&c->sel_work, &c->c_sel_work, (size_t)wtot) ||
-        dreserve(&c->sel_lists, &c->c_sel_lists, lb))
+    if (c->sel.reserve_amortised(total) || c->sel_work.reserve_amortised((size_t)wtot) || c->sel_lists.reserve_amortised(lb))
         return DPG_ERR_HIP;
-    if (hipMemcpy(c->sel_lists, woff.data(), sizeof(int64_t) * (size_t)ns, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(c->sel_lists + sizeof(int64_t) * (size_t)ns, S.level_list.data(), sizeof(int32_t) * (size_t)ns,
+    if (hipMemcpy(c->sel_lists.p, woff.data(), sizeof(int64_t) * (size_t)ns, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(c->sel_lists.p + sizeof(int64_t) * (size_t)ns, S.level_list.data(), sizeof(int32_t) * (size_t)ns,
                   hipMemcpyHostToDevice) != hipSuccess)
         return DPG_ERR_HIP;
     c->sel_gen = c->build_gen;
@@ -3007,29 +2931,29 @@ int selinv_run(CholDev* c, hipStream_t st, float* level_ms, int cap) {
     const int rc = selinv_prepare(c, st);
     if (rc) return rc;
     const dpg_chol_sym& S = c->sym;
-    const int64_t* woff = reinterpret_cast<const int64_t*>(c->sel_lists);
-    const int32_t* list = reinterpret_cast<const int32_t*>(c->sel_lists + sizeof(int64_t) * (size_t)S.ns);
+    const int64_t* woff = reinterpret_cast<const int64_t*>(c->sel_lists.p);
+    const int32_t* list = reinterpret_cast<const int32_t*>(c->sel_lists.p + sizeof(int64_t) * (size_t)S.ns);
     const bool timed = level_ms != nullptr;
     if (timed) {
         while ((int32_t)c->sel_ev.size() < S.n_levels + 1) {
-            hipEvent_t e;
-            if (hipEventCreate(&e) != hipSuccess) return DPG_ERR_HIP;
-            c->sel_ev.push_back(e);
+            DevEvent e;
+            if (e.ensure(hipEventDefault)) return DPG_ERR_HIP;
+            c->sel_ev.push_back(std::move(e));
         }
-        if (hipEventRecord(c->sel_ev[0], st) != hipSuccess) return DPG_ERR_HIP;
+        if (hipEventRecord(c->sel_ev[0].e, st) != hipSuccess) return DPG_ERR_HIP;
     }
     for (int32_t l = S.n_levels - 1, q = 1; l >= 0; --l, ++q) {
         const int32_t b = S.level_ptr[(size_t)l], n = S.level_ptr[(size_t)l + 1] - b;
         if (n > 0)
             hipLaunchKernelGGL(chol_selinv_level, dim3((unsigned)n), dim3(kT), c->sel_lds[(size_t)l], st, list + b, c->sns,
-                               c->relmap, woff, c->fronts, c->sel, c->sel_work);
-        if (timed && hipEventRecord(c->sel_ev[(size_t)q], st) != hipSuccess) return DPG_ERR_HIP;
+                               c->relmap, woff, c->fronts.p, c->sel.p, c->sel_work.p);
+        if (timed && hipEventRecord(c->sel_ev[(size_t)q].e, st) != hipSuccess) return DPG_ERR_HIP;
     }
     if (hipGetLastError() != hipSuccess) return DPG_ERR_HIP;
     if (timed) {
-        if (hipEventSynchronize(c->sel_ev[(size_t)S.n_levels]) != hipSuccess) return DPG_ERR_HIP;
+        if (hipEventSynchronize(c->sel_ev[(size_t)S.n_levels].e) != hipSuccess) return DPG_ERR_HIP;
         for (int32_t q = 0; q < S.n_levels && q < cap; ++q)
-            if (hipEventElapsedTime(level_ms + q, c->sel_ev[(size_t)q], c->sel_ev[(size_t)q + 1]) != hipSuccess)
+            if (hipEventElapsedTime(level_ms + q, c->sel_ev[(size_t)q].e, c->sel_ev[(size_t)q + 1].e) != hipSuccess)
                 return DPG_ERR_HIP;
     }
     return DPG_OK;
@@ -3088,7 +3012,7 @@ extern "C" int dpg_chol_selinv_gather(void* h, const int32_t* nodes, int64_t n, 
     CholDev* c = reinterpret_cast<CholDev*>(h);
     const int rc = dpg_chol_selinv_check(h, nodes, n, pairs, n_pairs);
     if (rc) return rc;
-    if (!c->sel || c->sel_gen != c->build_gen) return DPG_ERR_STATE;
+    if (!c->sel.p || c->sel_gen != c->build_gen) return DPG_ERR_STATE;
     const int64_t nb = n + n_pairs;
     if (nb == 0) return DPG_OK;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -3101,10 +3025,10 @@ extern "C" int dpg_chol_selinv_gather(void* h, const int32_t* nodes, int64_t n, 
     }
     for (int64_t q = 0; q < n_pairs; ++q) sel_locate(S, pairs[2 * q], pairs[2 * q + 1], &P[(size_t)(n + q)]);
     // (the list is rewritten per request: the previous request's kernel must be done with it)
-    if (hipStreamSynchronize(st) != hipSuccess || dreserve(&c->sel_picks, &c->c_sel_picks, (size_t)nb) ||
-        hipMemcpy(c->sel_picks, P.data(), sizeof(SelPick) * (size_t)nb, hipMemcpyHostToDevice) != hipSuccess)
+    if (hipStreamSynchronize(st) != hipSuccess || c->sel_picks.reserve_amortised((size_t)nb) ||
+        hipMemcpy(c->sel_picks.p, P.data(), sizeof(SelPick) * (size_t)nb, hipMemcpyHostToDevice) != hipSuccess)
         return DPG_ERR_HIP;
-    hipLaunchKernelGGL(chol_selinv_pick, dim3((unsigned)((9 * nb + 255) / 256)), dim3(256), 0, st, c->sel_picks, nb, c->sel,
+    hipLaunchKernelGGL(chol_selinv_pick, dim3((unsigned)((9 * nb + 255) / 256)), dim3(256), 0, st, c->sel_picks.p, nb, c->sel.p,
                        out_dev);
     return hipGetLastError() == hipSuccess ? DPG_OK : DPG_ERR_HIP;
 }
@@ -3119,12 +3043,12 @@ extern "C" int dpg_chol_marginals(void* h, const int32_t* nodes, int64_t n, cons
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int64_t nb = n + n_pairs;
     if ((rc = dpg_chol_selinv(h, stream))) return rc;
-    if (dreserve(&c->sel_out, &c->c_sel_out, (size_t)(9 * nb))) return DPG_ERR_HIP;
-    if ((rc = dpg_chol_selinv_gather(h, nodes, n, pairs, n_pairs, c->sel_out, stream))) return rc;
+    if (c->sel_out.reserve_amortised((size_t)(9 * nb))) return DPG_ERR_HIP;
+    if ((rc = dpg_chol_selinv_gather(h, nodes, n, pairs, n_pairs, c->sel_out.p, stream))) return rc;
     std::vector<double> tmp((size_t)(9 * nb));
     int32_t status = 0;
-    if (hipMemcpyAsync(&status, c->status, sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
-        (nb > 0 && hipMemcpyAsync(tmp.data(), c->sel_out, sizeof(double) * 9 * (size_t)nb, hipMemcpyDeviceToHost, st) !=
+    if (hipMemcpyAsync(&status, c->status.p, sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        (nb > 0 && hipMemcpyAsync(tmp.data(), c->sel_out.p, sizeof(double) * 9 * (size_t)nb, hipMemcpyDeviceToHost, st) !=
                        hipSuccess) ||
         hipStreamSynchronize(st) != hipSuccess)
         return DPG_ERR_HIP;
@@ -3137,7 +3061,7 @@ extern "C" int dpg_chol_marginals(void* h, const int32_t* nodes, int64_t n, cons
 
 extern "C" int64_t dpg_chol_selinv_bytes(void* h) {
     const CholDev* c = reinterpret_cast<const CholDev*>(h);
-    return c ? (int64_t)(sizeof(double) * (c->c_sel + c->c_sel_work)) : 0;
+    return c ? (int64_t)(sizeof(double) * (c->sel.cap + c->sel_work.cap)) : 0;
 }
 
 // ---- joint marginals: host side ----
@@ -3166,36 +3090,36 @@ extern "C" int dpg_chol_joint(void* h, int by_nodes, const int32_t* idx, int64_t
     const unsigned grid = (unsigned)std::min<int64_t>(nq, kPathGrid);
     const size_t pb = sizeof(PathPair) * (size_t)np, qb = sizeof(PathQuery) * (size_t)nq;
     // (the lists are rewritten per request: an earlier request's kernels must be done with them)
-    if (hipStreamSynchronize(st) != hipSuccess || dreserve(&c->jt_w, &c->c_jt_w, (size_t)J.w_total) ||
-        dreserve(&c->jt_work, &c->c_jt_work, in_lds ? 1 : (size_t)grid * 6 * (size_t)ldv) ||
-        dreserve(&c->jt_out, &c->c_jt_out, (size_t)J.out_total) || dreserve(&c->jt_lists, &c->c_jt_lists, pb + qb) ||
-        hipMemcpy(c->jt_lists, J.pairs.data(), pb, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(c->jt_lists + pb, J.queries.data(), qb, hipMemcpyHostToDevice) != hipSuccess)
+    if (hipStreamSynchronize(st) != hipSuccess || c->jt_w.reserve_amortised((size_t)J.w_total) ||
+        c->jt_work.reserve_amortised(in_lds ? 1 : (size_t)grid * 6 * (size_t)ldv) ||
+        c->jt_out.reserve_amortised((size_t)J.out_total) || c->jt_lists.reserve_amortised(pb + qb) ||
+        hipMemcpy(c->jt_lists.p, J.pairs.data(), pb, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(c->jt_lists.p + pb, J.queries.data(), qb, hipMemcpyHostToDevice) != hipSuccess)
         return DPG_ERR_HIP;
     if (ms)
-        for (hipEvent_t& e : c->jt_ev)
-            if (!e && hipEventCreate(&e) != hipSuccess) return DPG_ERR_HIP;
-    const PathPair* pairs = reinterpret_cast<const PathPair*>(c->jt_lists);
-    const PathQuery* queries = reinterpret_cast<const PathQuery*>(c->jt_lists + pb);
-    if (ms && hipEventRecord(c->jt_ev[0], st) != hipSuccess) return DPG_ERR_HIP;
+        for (DevEvent& e : c->jt_ev)
+            if (e.ensure(hipEventDefault)) return DPG_ERR_HIP;
+    const PathPair* pairs = reinterpret_cast<const PathPair*>(c->jt_lists.p);
+    const PathQuery* queries = reinterpret_cast<const PathQuery*>(c->jt_lists.p + pb);
+    if (ms && hipEventRecord(c->jt_ev[0].e, st) != hipSuccess) return DPG_ERR_HIP;
     hipLaunchKernelGGL(chol_path_forward, dim3(grid), dim3(kT), in_lds ? sizeof(double) * 6 * (size_t)ldv : 0, st, queries, nq,
-                       c->sns, c->relmap, c->fronts, c->jt_w, c->jt_work, ldv, in_lds ? 1 : 0);
-    if (ms && hipEventRecord(c->jt_ev[1], st) != hipSuccess) return DPG_ERR_HIP;
-    hipLaunchKernelGGL(chol_path_dot, dim3((unsigned)((np + 3) / 4)), dim3(256), 0, st, pairs, np, c->jt_w, c->jt_out,
+                       c->sns, c->relmap, c->fronts.p, c->jt_w.p, c->jt_work.p, ldv, in_lds ? 1 : 0);
+    if (ms && hipEventRecord(c->jt_ev[1].e, st) != hipSuccess) return DPG_ERR_HIP;
+    hipLaunchKernelGGL(chol_path_dot, dim3((unsigned)((np + 3) / 4)), dim3(256), 0, st, pairs, np, c->jt_w.p, c->jt_out.p,
                        (int64_t)J.ld);
-    if (ms && hipEventRecord(c->jt_ev[2], st) != hipSuccess) return DPG_ERR_HIP;
+    if (ms && hipEventRecord(c->jt_ev[2].e, st) != hipSuccess) return DPG_ERR_HIP;
     if (hipGetLastError() != hipSuccess) return DPG_ERR_HIP;
     std::vector<double> tmp((size_t)J.out_total);
     int32_t status = 0;
-    if (hipMemcpyAsync(&status, c->status, sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(tmp.data(), c->jt_out, sizeof(double) * tmp.size(), hipMemcpyDeviceToHost, st) != hipSuccess ||
+    if (hipMemcpyAsync(&status, c->status.p, sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(tmp.data(), c->jt_out.p, sizeof(double) * tmp.size(), hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess)
         return DPG_ERR_HIP;
     if (status != 0) return DPG_ERR_NUMERIC;
     for (double v : tmp)
         if (!(v == v)) return DPG_ERR_NUMERIC;
-    if (ms && (hipEventElapsedTime(ms, c->jt_ev[0], c->jt_ev[1]) != hipSuccess ||
-               hipEventElapsedTime(ms + 1, c->jt_ev[1], c->jt_ev[2]) != hipSuccess))
+    if (ms && (hipEventElapsedTime(ms, c->jt_ev[0].e, c->jt_ev[1].e) != hipSuccess ||
+               hipEventElapsedTime(ms + 1, c->jt_ev[1].e, c->jt_ev[2].e) != hipSuccess))
         return DPG_ERR_HIP;
     memcpy(host_out, tmp.data(), sizeof(double) * tmp.size());
     return DPG_OK;

@@ -9,6 +9,7 @@
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
+#include <string.h>
 #include <time.h>
 
 #include <algorithm>
@@ -23,6 +24,7 @@
 #include <vector>
 
 #include "../../include/dpg_slam_c.h"
+#include "dpg_buf.h"
 #include "dpg_chol.h"
 #include "dpg_gn_pipe.h"
 #include "dpg_internal.h"
@@ -53,48 +55,54 @@ T or_default(const T* p, void (*def)(T*)) {
     return v;
 }
 
-// A device array that owns its memory: freed when its owner goes, with the owner's device current.
+// The two memory kinds of OwnedBuf (dpg_buf.h): device memory, whose copy is stream-ordered and
+// waited for, and default-flags pinned host memory.
+struct DevMem {
+    typedef hipStream_t stream_t;
+    static int alloc(void** p, size_t bytes) { return hipMalloc(p, bytes) != hipSuccess; }
+    static void free(void* p) { (void)hipFree(p); }
+    static int copy(void* dst, const void* src, size_t bytes, hipStream_t s) {
+        return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+               hipStreamSynchronize(s) != hipSuccess;
+    }
+};
+struct PinMem {
+    typedef hipStream_t stream_t;
+    static int alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault) != hipSuccess; }
+    static void free(void* p) { (void)hipHostFree(p); }
+    static int copy(void* dst, const void* src, size_t bytes, hipStream_t) {
+        memcpy(dst, src, bytes);
+        return 0;
+    }
+};
 template <typename T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t cap = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
-    DevBuf& operator=(DevBuf&& o) noexcept {
-        std::swap(p, o.p);
-        std::swap(cap, o.cap);
+using DevBuf = OwnedBuf<T, DevMem>;
+template <typename T>
+using PinBuf = OwnedBuf<T, PinMem>;
+
+// An event (a stream) that owns itself: created on first use, destroyed with its owner.  Move-only.
+struct DevEvent {
+    hipEvent_t e = nullptr;
+    DevEvent() = default;
+    DevEvent(const DevEvent&) = delete;
+    DevEvent& operator=(const DevEvent&) = delete;
+    DevEvent(DevEvent&& o) noexcept : e(o.e) { o.e = nullptr; }
+    DevEvent& operator=(DevEvent&& o) noexcept {
+        std::swap(e, o.e);
         return *this;
     }
-    ~DevBuf() { release(); }
-    int reserve(size_t n) {
-        if (n <= cap) return 0;
-        release();
-        if (hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return -1;
-        cap = n;
-        return 0;
+    ~DevEvent() {
+        if (e) (void)hipEventDestroy(e);
     }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-    // grow to n elements keeping the first `keep` (stream-ordered copy, synchronised)
-    int grow(size_t n, size_t keep, hipStream_t s) {
-        if (n <= cap) return 0;
-        const size_t nc = std::max(n, cap + cap / 2);
-        T* q = nullptr;
-        if (hipMalloc(reinterpret_cast<void**>(&q), nc * sizeof(T)) != hipSuccess) return -1;
-        if (p && keep && (hipMemcpyAsync(q, p, std::min(keep, cap) * sizeof(T), hipMemcpyDeviceToDevice, s) != hipSuccess ||
-                          hipStreamSynchronize(s) != hipSuccess)) {
-            (void)hipFree(q);
-            return -1;
-        }
-        if (p) (void)hipFree(p);
-        p = q;
-        cap = nc;
-        return 0;
+    int ensure(unsigned flags) { return e || hipEventCreateWithFlags(&e, flags) == hipSuccess ? 0 : -1; }
+};
+struct DevStream {
+    hipStream_t s = nullptr;
+    DevStream() = default;
+    DevStream(const DevStream&) = delete;
+    DevStream& operator=(const DevStream&) = delete;
+    ~DevStream() {
+        if (s) (void)hipStreamDestroy(s);
     }
 };
 
@@ -204,8 +212,7 @@ struct dpg_ctx {
 // object or an error; the destructor stops and joins the thread (its queue is empty once the
 // context's stream has drained), then frees, with the context's device current.
 struct dpg_ctx::HostColl {
-    double* buf = nullptr;           // pinned: the packed system, summed in place
-    size_t cap = 0;                  // doubles
+    PinBuf<double> buf;              // pinned: the packed system, summed in place
     uint32_t* flag = nullptr;        // host-mapped: the last tag the thread completed
     uint32_t* timed_out = nullptr;   // host-mapped: the wait kernel gave up (no tag in 120 s)
     hipEvent_t ev[2] = {nullptr, nullptr};

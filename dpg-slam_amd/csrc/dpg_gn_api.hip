@@ -140,7 +140,7 @@ static void host_coll_thread(dpg_ctx::HostColl* hp, int device, dpg_coll_ops ops
             h.jobs.pop_front();
         }
         int bad = hipEventSynchronize(job.second) != hipSuccess;
-        if (!bad && ops.allreduce_sum_f64(ops.user, h.buf, (int64_t)h.count)) bad = 1;
+        if (!bad && ops.allreduce_sum_f64(ops.user, h.buf.p, (int64_t)h.count)) bad = 1;
         if (bad) h.failed.store(1);
         std::atomic_thread_fence(std::memory_order_release);   // the sum before the tag
         __atomic_store_n(h.flag, job.first, __ATOMIC_RELEASE);
@@ -171,7 +171,6 @@ dpg_ctx::HostColl::~HostColl() {
     }
     cv.notify_all();
     if (th.joinable()) th.join();
-    if (buf) (void)hipHostFree(buf);
     if (flag) (void)hipHostFree(flag);
     for (auto& e : ev) if (e) (void)hipEventDestroy(e);
 }
@@ -183,17 +182,12 @@ static int coll_sum_hb_host_async(dpg_ctx* c) {
     int rc;
     if (!c->hc && (rc = dpg_ctx::HostColl::create(c, c->hc))) return rc;
     dpg_ctx::HostColl& h = *c->hc;
-    if (h.cap < count) {   // the thread is idle here: every posted job has completed (hc_drain)
-        if (h.buf) HIP_TRY(hipHostFree(h.buf));
-        h.buf = nullptr;
-        h.cap = 0;
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h.buf), sizeof(double) * count, hipHostMallocDefault));
-        h.cap = count;
-    }
+    // the thread is idle here: every posted job has completed (hc_drain)
+    if (h.buf.cap < count && h.buf.reserve(count)) return fail(DPG_ERR_HIP, "hipHostMalloc(collective buffer) failed");
     h.count = count;
     const uint32_t tag = ++h.next_tag;
     hipEvent_t ev = h.ev[tag & 1];
-    HIP_TRY(hipMemcpyAsync(h.buf, c->gn.hb_part, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(h.buf.p, c->gn.hb_part, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipEventRecord(ev, c->stream));
     {
         std::lock_guard<std::mutex> lk(h.mu);
@@ -203,7 +197,7 @@ static int coll_sum_hb_host_async(dpg_ctx* c) {
     h.cv.notify_all();
     rc = dpg_launch_host_wait(h.flag, tag, h.timed_out, c->stream);
     if (rc) return fail(rc, "host-collective wait launch failed");
-    HIP_TRY(hipMemcpyAsync(c->gn.hb_own, h.buf, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->gn.hb_own, h.buf.p, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
     return DPG_OK;
 }
 

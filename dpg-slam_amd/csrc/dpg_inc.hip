@@ -48,26 +48,6 @@ namespace {
 
 constexpr int kThreads = 256;
 
-template <typename T>
-int dgrow(T** d, size_t* cap, size_t n, hipStream_t s, size_t keep) {
-    n = std::max<size_t>(n, 1);
-    if (*d && n <= *cap) return DPG_OK;
-    const size_t nc = std::max(n, *cap + *cap / 2);
-    T* p = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&p), nc * sizeof(T)) != hipSuccess) return DPG_ERR_HIP;
-    if (*d && keep) {
-        if (hipMemcpyAsync(p, *d, std::min(keep, *cap) * sizeof(T), hipMemcpyDeviceToDevice, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) {
-            (void)hipFree(p);
-            return DPG_ERR_HIP;
-        }
-    }
-    if (*d) (void)hipFree(*d);
-    *d = p;
-    *cap = nc;
-    return DPG_OK;
-}
-
 // est = theta (+) x (Pose2 ChartAtOrigin retraction, as retract_kernel), x indexed by elimination
 // position; maxd[v] = max |x_v|; atomicMax of the largest into maxall
 __global__ void inc_estimate_kernel(const double* __restrict__ theta, const double* __restrict__ x,
@@ -175,28 +155,27 @@ struct dpg_inc {
     dpg_chol_opts opts;
     int64_t reorders = 0;
     // device
-    dpg_gn_dev g{};                            // assembly buffers + the Cholesky (g.chol)
-    size_t c_factors = 0, c_cptr = 0, c_clist = 0, c_hb = 0, c_partials = 0;
-    double* theta = nullptr;                   // [V][3] linearization points (g.poses aliases it)
-    double* est = nullptr;                     // [V][3] current estimate
-    double* maxd = nullptr;                    // [V] max |delta_v| of the last update
-    double* est_nxt = nullptr;                 // ISAM2 mode: the update's estimate and max |delta| are
-    double* maxd_nxt = nullptr;                // written here and swapped in once the solve succeeded
-    size_t c_est_nxt = 0, c_maxd_nxt = 0;
-    int32_t* cnt = nullptr;                    // relinearized variables of the last update
-    size_t c_theta = 0, c_est = 0, c_maxd = 0;
+    dpg_gn_dev g{};                            // the kernels' view: raw pointers into the buffers below + g.chol
+    DevBuf<dpg_factor> factors;                // what g's assembly pointers point into (set in inc_rebuild_lists)
+    DevBuf<int32_t> up_cptr, up_clist;
+    DevBuf<double> hb_own, partials, scal3;
+    PinBuf<double> scal3_host;
+    DevBuf<double> theta;                      // [V][3] linearization points (g.poses aliases it)
+    DevBuf<double> est;                        // [V][3] current estimate
+    DevBuf<double> maxd;                       // [V] max |delta_v| of the last update
+    DevBuf<double> est_nxt;                    // ISAM2 mode: the update's estimate and max |delta| are
+    DevBuf<double> maxd_nxt;                   // written here and swapped in once the solve succeeded
+    DevBuf<int32_t> cnt;                       // relinearized variables of the last update
     std::vector<dpg_factor> h_dev_factors;     // staging (Q1 scaling)
     int64_t n_dev_f = 0;                       // leading factors already on the device as given (no Q1)
-    int32_t* h_lists = nullptr;                // pinned staging of the contribution lists
-    size_t c_lists = 0;
-    hipEvent_t lists_ev = nullptr;             // recorded after the lists' copies
+    PinBuf<int32_t> h_lists;                   // pinned staging of the contribution lists
+    DevEvent lists_ev;                         // recorded after the lists' copies
     bool lists_ev_set = false;
     bool prepared = false;                     // inc_prepare ran for the coming update (its pairs are in)
     int64_t prep_new = 0;                      // ... for this many new nodes
     int64_t prep_pairs0 = 0;                   // number of unique pairs before that prepare (rollback)
-    double* theta_bak = nullptr;               // [V][3] theta before a relinearization (rollback)
-    double* est_bak = nullptr;                 // [V][3] estimate before a batch update (rollback)
-    size_t c_theta_bak = 0, c_est_bak = 0;
+    DevBuf<double> theta_bak;                  // [V][3] theta before a relinearization (rollback)
+    DevBuf<double> est_bak;                    // [V][3] estimate before a batch update (rollback)
     bool prep_reordered = false;
     // the next fresh order, computed on a worker thread from a snapshot of the graph taken
     // bg_lead() nodes before it is due, then extended by the nodes and pairs that arrived since
@@ -231,20 +210,10 @@ int inc_rebuild_lists(dpg_inc* q, hipStream_t s) {
     int64_t n_list = 0;
     for (int64_t k = 0; k < nf; ++k) n_list += q->F[(size_t)k].kind == DPG_FACTOR_BETWEEN ? 3 : 1;
     // the last rebuild's copies out of the staging buffer must be done before it is rewritten
-    if (q->lists_ev_set && hipEventSynchronize(q->lists_ev) != hipSuccess) return DPG_ERR_HIP;
-    const size_t need = (size_t)(nu + 1 + n_list);
-    if (need > q->c_lists) {
-        const size_t nc = std::max(need, q->c_lists + q->c_lists / 2) + 4096;
-        if (q->h_lists) {
-            (void)hipHostFree(q->h_lists);
-            q->h_lists = nullptr;
-            q->c_lists = 0;
-        }
-        if (hipHostMalloc(reinterpret_cast<void**>(&q->h_lists), nc * sizeof(int32_t)) != hipSuccess) return DPG_ERR_HIP;
-        q->c_lists = nc;
-    }
-    int32_t* cnt = q->h_lists;
-    int32_t* clist = q->h_lists + nu + 1;
+    if (q->lists_ev_set && hipEventSynchronize(q->lists_ev.e) != hipSuccess) return DPG_ERR_HIP;
+    if (q->h_lists.reserve_amortised((size_t)(nu + 1 + n_list), 4096)) return DPG_ERR_HIP;
+    int32_t* cnt = q->h_lists.p;
+    int32_t* clist = q->h_lists.p + nu + 1;
     std::fill(cnt, cnt + nu + 1, 0);
     for (int64_t k = 0; k < nf; ++k) {
         const dpg_factor& f = q->F[(size_t)k];
@@ -272,16 +241,21 @@ int inc_rebuild_lists(dpg_inc* q, hipStream_t s) {
     g.n_blocks_rows = (int32_t)nblk(n);
     const int64_t keep = q->P.duplicate_factors ? 0 : std::min(q->n_dev_f, nf);
     int rc = 0;
-    rc |= dgrow(&g.factors, &q->c_factors, (size_t)nf, s, (size_t)keep);
-    rc |= dgrow(&g.up_cptr, &q->c_cptr, (size_t)(nu + 1), s, 0);
-    rc |= dgrow(&g.up_clist, &q->c_clist, (size_t)n_list, s, 0);
-    rc |= dgrow(&g.hb_own, &q->c_hb, (size_t)(9 * nu + 3 * n + 2), s, 0);
-    rc |= dgrow(&g.partials, &q->c_partials, (size_t)(6 * g.n_blocks_rows + n), s, 0);
-    if (!g.scal3) {
-        rc |= hipMalloc(reinterpret_cast<void**>(&g.scal3), 4 * sizeof(double)) != hipSuccess;
-        if (!rc) rc |= hipHostMalloc(reinterpret_cast<void**>(&g.scal3_host), 4 * sizeof(double)) != hipSuccess;
-    }
+    // (a graph without factors still hands the kernels one element)
+    rc |= q->factors.grow((size_t)std::max<int64_t>(nf, 1), (size_t)keep, s);
+    rc |= q->up_cptr.grow((size_t)(nu + 1), 0, s);
+    rc |= q->up_clist.grow((size_t)std::max<int64_t>(n_list, 1), 0, s);
+    rc |= q->hb_own.grow((size_t)(9 * nu + 3 * n + 2), 0, s);
+    rc |= q->partials.grow((size_t)(6 * g.n_blocks_rows + n), 0, s);
+    rc |= q->scal3.reserve(4) || q->scal3_host.reserve(4);
     if (rc) return DPG_ERR_HIP;
+    g.factors = q->factors.p;
+    g.up_cptr = q->up_cptr.p;
+    g.up_clist = q->up_clist.p;
+    g.hb_own = q->hb_own.p;
+    g.partials = q->partials.p;
+    g.scal3 = q->scal3.p;
+    g.scal3_host = q->scal3_host.p;
     if (q->P.duplicate_factors) {   // factors as the device sees them: Q1 multiplicity folded into the information
         q->h_dev_factors = q->F;
         for (int64_t k = 0; k < nf; ++k) {
@@ -302,8 +276,7 @@ int inc_rebuild_lists(dpg_inc* q, hipStream_t s) {
         return DPG_ERR_HIP;
     if (n_list && hipMemcpyAsync(g.up_clist, clist, sizeof(int32_t) * (size_t)n_list, hipMemcpyHostToDevice, s) != hipSuccess)
         return DPG_ERR_HIP;
-    if (!q->lists_ev && hipEventCreateWithFlags(&q->lists_ev, hipEventDisableTiming) != hipSuccess) return DPG_ERR_HIP;
-    if (hipEventRecord(q->lists_ev, s) != hipSuccess) return DPG_ERR_HIP;
+    if (q->lists_ev.ensure(hipEventDisableTiming) || hipEventRecord(q->lists_ev.e, s) != hipSuccess) return DPG_ERR_HIP;
     q->lists_ev_set = true;
     return DPG_OK;
 }
@@ -418,15 +391,7 @@ int dpg_inc_abort_prepare(dpg_inc* q) {
 void dpg_inc_destroy(dpg_inc* q) {
     if (!q) return;
     dpg_ctx_release_child(q->ctx, q);
-    hipStream_t s = q->ctx->stream;
-    (void)hipStreamSynchronize(s);
-    void* ptrs[] = {q->g.factors, q->g.up_cptr, q->g.up_clist, q->g.hb_own, q->g.partials, q->g.scal3,
-                    q->theta, q->est, q->maxd, q->cnt, q->est_nxt, q->maxd_nxt, q->theta_bak, q->est_bak};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    if (q->g.scal3_host) (void)hipHostFree(q->g.scal3_host);
-    if (q->h_lists) (void)hipHostFree(q->h_lists);
-    if (q->lists_ev) (void)hipEventDestroy(q->lists_ev);
+    (void)hipStreamSynchronize(q->ctx->stream);
     if (q->g.chol) dpg_chol_destroy(q->g.chol);
     delete q;
 }
@@ -611,17 +576,17 @@ int dpg_inc_update(dpg_inc* q, int64_t n_new, const double* init, const dpg_fact
     if (V1 == 0) return set_err(DPG_ERR_STATE, "dpg_inc_update: empty graph");
     // device state for the new nodes (theta and the estimate start at the initial values)
     int rc = 0;
-    rc |= dgrow(&q->theta, &q->c_theta, (size_t)(3 * V1), s, (size_t)(3 * V0));
-    rc |= dgrow(&q->est, &q->c_est, (size_t)(3 * V1), s, (size_t)(3 * V0));
-    rc |= dgrow(&q->maxd, &q->c_maxd, (size_t)V1, s, (size_t)V0);
-    if (!q->cnt) rc |= hipMalloc(reinterpret_cast<void**>(&q->cnt), sizeof(int32_t)) != hipSuccess;
+    rc |= q->theta.grow((size_t)(3 * V1), (size_t)(3 * V0), s);
+    rc |= q->est.grow((size_t)(3 * V1), (size_t)(3 * V0), s);
+    rc |= q->maxd.grow((size_t)V1, (size_t)V0, s);
+    rc |= q->cnt.reserve(1);
     if (rc) return set_err(DPG_ERR_HIP, "dpg_inc_update: out of device memory");
     if (n_new > 0) {
-        if (hipMemcpyAsync(q->theta + 3 * V0, init, sizeof(double) * 3 * (size_t)n_new, hipMemcpyHostToDevice, s) !=
+        if (hipMemcpyAsync(q->theta.p + 3 * V0, init, sizeof(double) * 3 * (size_t)n_new, hipMemcpyHostToDevice, s) !=
                 hipSuccess ||
-            hipMemcpyAsync(q->est + 3 * V0, init, sizeof(double) * 3 * (size_t)n_new, hipMemcpyHostToDevice, s) !=
+            hipMemcpyAsync(q->est.p + 3 * V0, init, sizeof(double) * 3 * (size_t)n_new, hipMemcpyHostToDevice, s) !=
                 hipSuccess ||
-            hipMemsetAsync(q->maxd + V0, 0, sizeof(double) * (size_t)n_new, s) != hipSuccess)
+            hipMemsetAsync(q->maxd.p + V0, 0, sizeof(double) * (size_t)n_new, s) != hipSuccess)
             return set_err(DPG_ERR_HIP, "dpg_inc_update: upload failed");
     }
     // graph + symbolic state: the pairs of this update's Between factors are in the pattern already
@@ -672,8 +637,8 @@ int dpg_inc_update(dpg_inc* q, int64_t n_new, const double* init, const dpg_fact
         q->updates = upd0;
         q->prepared = true;   // the pairs this update added leave the pattern
         dpg_inc_abort_prepare(q);
-        if (theta_saved) (void)hipMemcpy(q->theta, q->theta_bak, sizeof(double) * 3 * (size_t)V0, hipMemcpyDeviceToDevice);
-        if (est_saved) (void)hipMemcpy(q->est, q->est_bak, sizeof(double) * 3 * (size_t)V0, hipMemcpyDeviceToDevice);
+        if (theta_saved) (void)hipMemcpy(q->theta.p, q->theta_bak.p, sizeof(double) * 3 * (size_t)V0, hipMemcpyDeviceToDevice);
+        if (est_saved) (void)hipMemcpy(q->est.p, q->est_bak.p, sizeof(double) * 3 * (size_t)V0, hipMemcpyDeviceToDevice);
         return set_err(code, msg);
     };
     // the contribution lists (and their copies on s) on the graph's helper thread while this one
@@ -705,20 +670,20 @@ int dpg_inc_update(dpg_inc* q, int64_t n_new, const double* init, const dpg_fact
     if (q->P.mode == DPG_INC_ISAM2) {
         // 1. relinearize the variables whose delta passed the threshold (before the new factors)
         if (relin) {
-            if (dgrow(&q->theta_bak, &q->c_theta_bak, (size_t)(3 * V0), s, 0) ||
-                hipMemcpyAsync(q->theta_bak, q->theta, sizeof(double) * 3 * (size_t)V0, hipMemcpyDeviceToDevice, s) !=
+            if (q->theta_bak.grow((size_t)(3 * V0), 0, s) ||
+                hipMemcpyAsync(q->theta_bak.p, q->theta.p, sizeof(double) * 3 * (size_t)V0, hipMemcpyDeviceToDevice, s) !=
                     hipSuccess)
                 return rollback(DPG_ERR_HIP, "dpg_inc_update: theta snapshot failed");
             theta_saved = true;
-            if (hipMemsetAsync(q->cnt, 0, sizeof(int32_t), s) != hipSuccess) return rollback(DPG_ERR_HIP, "memset");
-            hipLaunchKernelGGL(inc_relin_kernel, dim3(nblk(V0)), dim3(kThreads), 0, s, q->theta, q->est, q->maxd, V0,
-                               q->P.relinearize_threshold, q->cnt);
+            if (hipMemsetAsync(q->cnt.p, 0, sizeof(int32_t), s) != hipSuccess) return rollback(DPG_ERR_HIP, "memset");
+            hipLaunchKernelGGL(inc_relin_kernel, dim3(nblk(V0)), dim3(kThreads), 0, s, q->theta.p, q->est.p, q->maxd.p, V0,
+                               q->P.relinearize_threshold, q->cnt.p);
         }
         // 2. linearize everything at theta, factor, solve, estimate = theta (+) delta (into the
         //    spare buffers: the current estimate stays intact until the solve is known good)
-        if (dgrow(&q->est_nxt, &q->c_est_nxt, (size_t)(3 * V1), s, 0) || dgrow(&q->maxd_nxt, &q->c_maxd_nxt, (size_t)V1, s, 0))
+        if (q->est_nxt.grow((size_t)(3 * V1), 0, s) || q->maxd_nxt.grow((size_t)V1, 0, s))
             return rollback(DPG_ERR_HIP, "dpg_inc_update: out of device memory");
-        q->g.poses = q->theta;
+        q->g.poses = q->theta.p;
         if ((rc = dpg_gn_dev_assemble(&q->g, q->g.hb_own, s))) return rollback(rc, "assembly failed");
         // isam_->update's partial re-elimination: between reorders and relinearizations every H
         // block is the same sum at the same theta unless a new factor or pair touches its nodes, so
@@ -749,27 +714,25 @@ int dpg_inc_update(dpg_inc* q, int64_t n_new, const double* init, const dpg_fact
             q->prof[11] = (double)pst[3] * 1e-6;
         }
         if (hipMemsetAsync(q->g.scal3, 0, sizeof(double), s) != hipSuccess) return rollback(DPG_ERR_HIP, "memset");
-        hipLaunchKernelGGL(inc_estimate_kernel, dim3(nblk(V1)), dim3(kThreads), 0, s, q->theta, dpg_chol_x_dev(q->g.chol),
-                           dpg_chol_pos_dev(q->g.chol), V1, q->est_nxt, q->maxd_nxt, q->g.scal3);
+        hipLaunchKernelGGL(inc_estimate_kernel, dim3(nblk(V1)), dim3(kThreads), 0, s, q->theta.p, dpg_chol_x_dev(q->g.chol),
+                           dpg_chol_pos_dev(q->g.chol), V1, q->est_nxt.p, q->maxd_nxt.p, q->g.scal3);
         double sc[3];
         q->g.last_used_chol = 1;
         if ((rc = dpg_gn_dev_fetch(&q->g, q->g.hb_own, s, sc))) return rollback(rc, "fetch failed");
         if (sc[2] != 0.0) return rollback(DPG_ERR_NUMERIC, "dpg_inc_update: Cholesky failed (H not positive definite)");
         // every read that can fail before the commit: a failure rolls the whole update back
         int32_t nrel = 0;
-        if (relin && hipMemcpy(&nrel, q->cnt, sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
+        if (relin && hipMemcpy(&nrel, q->cnt.p, sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
             return rollback(DPG_ERR_HIP, "dpg_inc_update: relinearized-count read-back failed");
         std::swap(q->est, q->est_nxt);
-        std::swap(q->c_est, q->c_est_nxt);
         std::swap(q->maxd, q->maxd_nxt);
-        std::swap(q->c_maxd, q->c_maxd_nxt);
         S.relinearized = nrel;
         S.gn_iterations = 1;
         S.error = sc[1];
         S.last_delta_inf = sc[0];
     } else {
         // batch Gauss-Newton to convergence from the current estimates
-        q->g.poses = q->est;
+        q->g.poses = q->est.p;
         q->g.have_factor = 0;
         q->g.last_delta_inf = 1e300;
         q->g.prev_delta_inf = 1e300;
@@ -779,8 +742,8 @@ int dpg_inc_update(dpg_inc* q, int64_t n_new, const double* init, const dpg_fact
         double sc[3] = {0, 0, 0};
         int it = 0;
         if (V0 > 0) {
-            if (dgrow(&q->est_bak, &q->c_est_bak, (size_t)(3 * V0), s, 0) ||
-                hipMemcpyAsync(q->est_bak, q->est, sizeof(double) * 3 * (size_t)V0, hipMemcpyDeviceToDevice, s) != hipSuccess)
+            if (q->est_bak.grow((size_t)(3 * V0), 0, s) ||
+                hipMemcpyAsync(q->est_bak.p, q->est.p, sizeof(double) * 3 * (size_t)V0, hipMemcpyDeviceToDevice, s) != hipSuccess)
                 return rollback(DPG_ERR_HIP, "dpg_inc_update: estimate snapshot failed");
             est_saved = true;
         }
@@ -794,7 +757,7 @@ int dpg_inc_update(dpg_inc* q, int64_t n_new, const double* init, const dpg_fact
             if (sc[0] < gp.delta_tol) break;
         }
         // theta follows the estimate (a batch solve relinearizes everything)
-        if (hipMemcpyAsync(q->theta, q->est, sizeof(double) * 3 * (size_t)V1, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+        if (hipMemcpyAsync(q->theta.p, q->est.p, sizeof(double) * 3 * (size_t)V1, hipMemcpyDeviceToDevice, s) != hipSuccess ||
             hipStreamSynchronize(s) != hipSuccess)
             return set_err(DPG_ERR_HIP, "copy failed");
         S.gn_iterations = it;
@@ -854,9 +817,9 @@ int dpg_inc_save(dpg_inc* q, const char* path) {
     std::vector<double> theta(3 * V), est(3 * V), maxd(V);
     hipStream_t s = q->ctx->stream;
     if (hipSetDevice(q->ctx->device) != hipSuccess) return set_err(DPG_ERR_HIP, "hipSetDevice failed");
-    if (V && (hipMemcpyAsync(theta.data(), q->theta, sizeof(double) * 3 * V, hipMemcpyDeviceToHost, s) != hipSuccess ||
-              hipMemcpyAsync(est.data(), q->est, sizeof(double) * 3 * V, hipMemcpyDeviceToHost, s) != hipSuccess ||
-              hipMemcpyAsync(maxd.data(), q->maxd, sizeof(double) * V, hipMemcpyDeviceToHost, s) != hipSuccess))
+    if (V && (hipMemcpyAsync(theta.data(), q->theta.p, sizeof(double) * 3 * V, hipMemcpyDeviceToHost, s) != hipSuccess ||
+              hipMemcpyAsync(est.data(), q->est.p, sizeof(double) * 3 * V, hipMemcpyDeviceToHost, s) != hipSuccess ||
+              hipMemcpyAsync(maxd.data(), q->maxd.p, sizeof(double) * V, hipMemcpyDeviceToHost, s) != hipSuccess))
         return set_err(DPG_ERR_HIP, "dpg_inc_save: read-back failed");
     if (hipStreamSynchronize(s) != hipSuccess) return set_err(DPG_ERR_HIP, "dpg_inc_save: read-back failed");
     std::vector<int64_t> off((size_t)h.n_scans + 1, 0);
@@ -898,9 +861,9 @@ int64_t dpg_inc_export(dpg_inc* q, int64_t* updates, dpg_factor* F, int32_t* cre
     hipStream_t s = q->ctx->stream;
     if (V && (theta || est || maxd)) {
         if (hipSetDevice(q->ctx->device) != hipSuccess) return set_err(DPG_ERR_HIP, "hipSetDevice failed");
-        if ((theta && hipMemcpyAsync(theta, q->theta, sizeof(double) * 3 * V, hipMemcpyDeviceToHost, s) != hipSuccess) ||
-            (est && hipMemcpyAsync(est, q->est, sizeof(double) * 3 * V, hipMemcpyDeviceToHost, s) != hipSuccess) ||
-            (maxd && hipMemcpyAsync(maxd, q->maxd, sizeof(double) * V, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+        if ((theta && hipMemcpyAsync(theta, q->theta.p, sizeof(double) * 3 * V, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+            (est && hipMemcpyAsync(est, q->est.p, sizeof(double) * 3 * V, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+            (maxd && hipMemcpyAsync(maxd, q->maxd.p, sizeof(double) * V, hipMemcpyDeviceToHost, s) != hipSuccess) ||
             hipStreamSynchronize(s) != hipSuccess)
             return set_err(DPG_ERR_HIP, "dpg_inc_export: read-back failed");
     }
@@ -1012,14 +975,14 @@ dpg_inc* dpg_inc_load(dpg_ctx* ctx, const char* path) {
     hipStream_t s = ctx->stream;
     if (hipSetDevice(ctx->device) != hipSuccess) return bail(DPG_ERR_HIP, "hipSetDevice failed");
     int rc = 0;
-    rc |= dgrow(&q->theta, &q->c_theta, 3 * V, s, 0);
-    rc |= dgrow(&q->est, &q->c_est, 3 * V, s, 0);
-    rc |= dgrow(&q->maxd, &q->c_maxd, V, s, 0);
-    if (!q->cnt) rc |= hipMalloc(reinterpret_cast<void**>(&q->cnt), sizeof(int32_t)) != hipSuccess;
+    rc |= q->theta.grow(3 * V, 0, s);
+    rc |= q->est.grow(3 * V, 0, s);
+    rc |= q->maxd.grow(V, 0, s);
+    rc |= q->cnt.reserve(1);
     if (rc) return bail(DPG_ERR_HIP, "dpg_inc_load: out of device memory");
-    if (hipMemcpyAsync(q->theta, theta.data(), sizeof(double) * 3 * V, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(q->est, est.data(), sizeof(double) * 3 * V, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(q->maxd, maxd.data(), sizeof(double) * V, hipMemcpyHostToDevice, s) != hipSuccess)
+    if (hipMemcpyAsync(q->theta.p, theta.data(), sizeof(double) * 3 * V, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(q->est.p, est.data(), sizeof(double) * 3 * V, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(q->maxd.p, maxd.data(), sizeof(double) * V, hipMemcpyHostToDevice, s) != hipSuccess)
         return bail(DPG_ERR_HIP, "dpg_inc_load: upload failed");
     if ((rc = inc_rebuild(q, s))) return bail(rc, "dpg_inc_load: solver rebuild failed");
     if (hipStreamSynchronize(s) != hipSuccess) return bail(DPG_ERR_HIP, "dpg_inc_load: upload failed");
@@ -1030,7 +993,7 @@ int dpg_inc_get_poses(dpg_inc* q, double* poses, int64_t n) {
     if (!q || !poses || n < 0 || n > q->V) return set_err(DPG_ERR_ARG, "dpg_inc_get_poses: bad arguments");
     if (n == 0) return DPG_OK;
     hipStream_t s = q->ctx->stream;
-    if (hipMemcpyAsync(poses, q->est, sizeof(double) * 3 * (size_t)n, hipMemcpyDeviceToHost, s) != hipSuccess ||
+    if (hipMemcpyAsync(poses, q->est.p, sizeof(double) * 3 * (size_t)n, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)
         return set_err(DPG_ERR_HIP, "dpg_inc_get_poses: copy failed");
     return DPG_OK;
@@ -1105,7 +1068,7 @@ int dpg_inc_relative_covariances(dpg_inc* q, const int32_t* pairs, int64_t n, do
     if ((rc = inc_joint_blocks(q, fn, 0, tri.data(), 3 * n, blocks.data()))) return rc;
     std::vector<double> X((size_t)(3 * q->V));
     hipStream_t s = q->ctx->stream;
-    if (hipMemcpyAsync(X.data(), q->theta, sizeof(double) * X.size(), hipMemcpyDeviceToHost, s) != hipSuccess ||
+    if (hipMemcpyAsync(X.data(), q->theta.p, sizeof(double) * X.size(), hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)
         return set_err(DPG_ERR_HIP, "dpg_inc_relative_covariances: copy failed");
     dpg_relative_from_blocks(pairs, n, X.data(), blocks.data(), cov_out);

@@ -40,3 +40,35 @@ def test_destroy_with_live_children_then_fresh_context():
         X, st = fresh.optimize_graph(X0, F)
         # zero-residual optimum, fp64 Gauss-Newton to its default step tolerance (as smoke())
         assert st.iterations > 0 and np.abs(pose_diff(X, X_opt)).max() < 1e-9, X
+
+
+@pytest.mark.gpu
+def test_destroy_with_every_lazy_resource_allocated():
+    """The same with everything that is created on first use in existence: the solver's selected
+    inverse, pick and joint-marginal buffers (marginals and a joint marginal of the incremental
+    graph), the store's grid buffers (an occupancy grid) and, on the context's own graph, L11^-1
+    with the stream and events it is computed on (a batch solve with solve_inv_cols = 1).  Each owner
+    releases what it holds; a fresh context then solves as before."""
+    from dpgslam import api
+    from graphs import pose_diff
+    X0, F, X_opt = _two_node_graph()
+    ctx = api.Context(0)
+    inc = api.IncGraph(ctx)
+    inc.update(X0, F)
+    assert inc.marginals().shape == (2, 3, 3) and inc.joint_marginal([1, 0]).shape == (6, 6)
+    ranges = np.full((2, 16), 5.0, np.float32)
+    geom = np.tile(np.array([-np.pi, np.pi, 8.0], np.float32), (2, 1))
+    store = api.DpgStore(ctx, ranges, geom)
+    assert (store.occupancy_grid(2, np.zeros((2, 3), np.float32))["data"] == 100).any()
+    ctx.set_solver_options(solve_inv_cols=1)
+    X, st = ctx.optimize_graph(X0, F)
+    assert st.iterations > 0 and np.abs(pose_diff(X, X_opt)).max() < 1e-9, X
+    api.lib().dpg_ctx_destroy(ctx.handle)
+    ctx.handle = None
+    for child in (inc, store):
+        child.close()
+        assert child.handle is None
+    ctx.close()
+    with api.Context(0) as fresh:
+        X, st = fresh.optimize_graph(X0, F)
+        assert st.iterations > 0 and np.abs(pose_diff(X, X_opt)).max() < 1e-9, X

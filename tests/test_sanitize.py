@@ -4,7 +4,8 @@ sanitize` builds the oracle, the ABI's host half (csrc/dpg_host.c), the workload
 (csrc/dpg_chol_plan.cpp) with -fsanitize=address,undefined -fno-sanitize-recover=all and runs
 tools/sanitize_check.cpp through them (scans -> clouds -> ICP -> GN -> symbolic analysis, full and
 incremental -> solver plans of a mesh with team fronts and of a loop graph, every option set ->
-DPG change detection); any report fails the run."""
+DPG change detection), after the growth rules and ownership of the GPU layer's buffer template
+(csrc/dpg_buf.h) over a counting malloc policy; any report fails the run."""
 import os
 import subprocess
 
@@ -14,4 +15,4 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_host_code_under_asan_ubsan():
     r = subprocess.run(["make", "-C", os.path.join(ROOT, "oracle"), "sanitize"], capture_output=True, text=True,
                        timeout=600)
-    assert r.returncode == 0 and "sanitize check ok" in r.stdout and "solver plans ok" in r.stdout, (r.stdout + r.stderr)[-4000:]
+    assert r.returncode == 0 and "sanitize check ok" in r.stdout and "solver plans ok" in r.stdout and "buffers ok" in r.stdout, (r.stdout + r.stderr)[-4000:]

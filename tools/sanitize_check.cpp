@@ -5,14 +5,17 @@
 // incremental (csrc/dpg_chol_sym.cpp), and the GPU solver's host planner (csrc/dpg_chol_plan.cpp:
 // its tables are followed by the kernels without bounds checks), driven through a small
 // end-to-end workload: scans -> clouds -> batched ICP + covariance -> factors -> Gauss-Newton ->
-// symbolic analysis -> solver plans -> DPG change detection over two passes.  Any sanitizer report
-// aborts (-fno-sanitize-recover).
+// symbolic analysis -> solver plans -> DPG change detection over two passes; and the owning buffer
+// template of the GPU layer (csrc/dpg_buf.h) over host memory.  Any sanitizer report aborts
+// (-fno-sanitize-recover).
 #include <math.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <vector>
 
+#include "../dpg-slam_amd/csrc/dpg_buf.h"
 #include "../dpg-slam_amd/csrc/dpg_chol.h"
 #include "../dpg-slam_amd/csrc/dpg_chol_plan.h"
 #include "../dpg-slam_amd/csrc/dpg_internal.h"
@@ -101,7 +104,108 @@ static int plan_checks() {
     return 0;
 }
 
+// OwnedBuf's growth rules and ownership over malloc / free / memcpy: the policy counts allocations
+// and live bytes (the size sits in a 16-byte header before each block) and can be told to fail the
+// next allocation.
+struct HostMem {
+    typedef int stream_t;
+    static int allocs, fail_next;
+    static size_t live;
+    static int alloc(void** p, size_t bytes) {
+        if (fail_next) { fail_next = 0; return -1; }
+        char* b = static_cast<char*>(malloc(bytes + 16));
+        if (!b) return -1;
+        memcpy(b, &bytes, sizeof(bytes));
+        ++allocs;
+        live += bytes;
+        *p = b + 16;
+        return 0;
+    }
+    static void free(void* p) {
+        char* b = static_cast<char*>(p) - 16;
+        size_t bytes;
+        memcpy(&bytes, b, sizeof(bytes));
+        live -= bytes;
+        ::free(b);
+    }
+    static int copy(void* dst, const void* src, size_t bytes, int) {
+        memcpy(dst, src, bytes);
+        return 0;
+    }
+};
+int HostMem::allocs = 0, HostMem::fail_next = 0;
+size_t HostMem::live = 0;
+
+static int buffer_checks() {
+    typedef OwnedBuf<int32_t, HostMem> Buf;
+    {   // (a) the amortised rule from empty, max(n, cap + cap / 2): 13 allocations for n = 1..100
+        const size_t want[13] = {1, 2, 3, 4, 6, 9, 13, 19, 28, 42, 63, 94, 141};
+        Buf b;
+        int k = 0;
+        for (size_t n = 1; n <= 100; ++n) {
+            const int before = HostMem::allocs;
+            REQUIRE(b.reserve_amortised(n) == 0 && b.p && b.cap >= n);
+            if (HostMem::allocs != before) {
+                REQUIRE(HostMem::allocs == before + 1 && k < 13 && b.cap == want[k]);
+                ++k;
+            }
+            REQUIRE(HostMem::live == b.cap * sizeof(int32_t));   // released first: one buffer at any time
+        }
+        REQUIRE(k == 13);
+        // with slack every capacity is the rule's value (from the capacity held) plus the slack: for
+        // n = 1..100 that is one allocation of 1 + 4096, and past it the 1.5x step or n, plus 4096
+        Buf c;
+        const int a0 = HostMem::allocs;
+        for (size_t n = 0; n <= 100; ++n) REQUIRE(c.reserve_amortised(n, 4096) == 0 && c.cap == 1 + 4096);
+        REQUIRE(HostMem::allocs == a0 + 1);
+        const size_t ask[5] = {4098, 6000, 20000, 20001, 40000};
+        const size_t get[5] = {4097 + 2048 + 4096, 10241, 20000 + 4096, 24096, 40000 + 4096};   // 1.5x, -, n, -, n
+        for (int q = 0; q < 5; ++q) REQUIRE(c.reserve_amortised(ask[q], 4096) == 0 && c.cap == get[q]);
+        REQUIRE(HostMem::allocs == a0 + 4 && HostMem::live == (b.cap + c.cap) * sizeof(int32_t));
+        // (c) a failed amortised reserve leaves the buffer empty
+        HostMem::fail_next = 1;
+        REQUIRE(c.reserve_amortised(100000) == -1 && c.p == nullptr && c.cap == 0);
+        REQUIRE(c.reserve(0) == 0 && c.p == nullptr);   // exact form: nothing asked of an empty buffer, nothing made
+        REQUIRE(c.reserve(7) == 0 && c.cap == 7 && c.reserve(5) == 0 && c.cap == 7);
+    }
+    REQUIRE(HostMem::live == 0);
+    {   // (b) grow keeps the first min(keep, old capacity) elements; a failed grow changes nothing
+        Buf b;
+        REQUIRE(b.grow(0, 0, 0) == 0 && b.p == nullptr);   // (no clamp: the callers that can ask for 0 clamp)
+        REQUIRE(b.grow(10, 0, 0) == 0 && b.cap == 10);
+        for (int i = 0; i < 10; ++i) b.p[i] = 1000 + i;
+        REQUIRE(b.grow(11, 6, 0) == 0 && b.cap == 15);    // 10 + 10 / 2
+        for (int i = 0; i < 6; ++i) REQUIRE(b.p[i] == 1000 + i);
+        for (int i = 6; i < 15; ++i) b.p[i] = 2000 + i;
+        REQUIRE(b.grow(100, 1000, 0) == 0 && b.cap == 100);   // keep past the old capacity: all 15 kept
+        for (int i = 0; i < 15; ++i) REQUIRE(b.p[i] == (i < 6 ? 1000 : 2000) + i);
+        int32_t* p0 = b.p;
+        HostMem::fail_next = 1;
+        REQUIRE(b.grow(1000, 15, 0) == -1 && b.p == p0 && b.cap == 100);
+        for (int i = 0; i < 15; ++i) REQUIRE(b.p[i] == (i < 6 ? 1000 : 2000) + i);
+        REQUIRE(b.grow(100, 15, 0) == 0 && b.p == p0);        // nothing to do
+        // (d) one owner per allocation through move construction, move assignment and std::swap
+        const size_t live1 = HostMem::live;
+        Buf m(std::move(b));
+        REQUIRE(b.p == nullptr && b.cap == 0 && m.p == p0 && m.cap == 100 && HostMem::live == live1);
+        Buf o;
+        REQUIRE(o.reserve(3) == 0);
+        int32_t* p1 = o.p;
+        o = std::move(m);   // move-assignment swaps: the moved-from buffer owns the other allocation
+        REQUIRE(o.p == p0 && o.cap == 100 && m.p == p1 && m.cap == 3);
+        std::swap(o, m);
+        REQUIRE(o.p == p1 && o.cap == 3 && m.p == p0 && m.cap == 100);
+        REQUIRE(HostMem::live == (100 + 3) * sizeof(int32_t));
+        m.release();
+        REQUIRE(m.p == nullptr && m.cap == 0 && HostMem::live == 3 * sizeof(int32_t));
+    }
+    REQUIRE(HostMem::live == 0 && HostMem::fail_next == 0);
+    printf("buffers ok: %d allocations, none live\n", HostMem::allocs);
+    return 0;
+}
+
 int main() {
+    REQUIRE(buffer_checks() == 0);
     const int V = 24, NB = 720;
     const float W = 20.f, amin = (float)-M_PI, amax = (float)M_PI, rmax = 12.f;
     std::vector<float> segs(4 * 512);
