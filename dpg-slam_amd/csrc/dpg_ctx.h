@@ -197,6 +197,15 @@ struct dpg_ctx {
     DevBuf<int32_t> shard_idx;       // per device context: its shard's caller indices
     DevBuf<float> cost_dev;          // rank form: the all-reduced cost vector of a batch
     dpg_chol_opts copts;             // solver options (dpg_ctx_set_solver_options)
+    // correlative scan matching (dpg_csm.hip): pair records, rotation tables, the smoothing stencil,
+    // results, and the diagnostic output (table bytes / score volume); the events around its kernel
+    DevBuf<dpg_csm_pair> csm_pairs;
+    DevBuf<float> csm_rot;
+    DevBuf<int32_t> csm_stencil;
+    DevBuf<dpg_csm_result> csm_res;
+    DevBuf<int32_t> csm_diag;
+    DevEvent csm_ev[2];
+    bool csm_timed = false;
 };
 
 // The rank form over the caller's collectives (kCollHost) in the pipelined Gauss-Newton loop: the

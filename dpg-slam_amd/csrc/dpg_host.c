@@ -165,6 +165,56 @@ int dpg_grid_box(const float* lidar_xy, const float* r_v, const uint8_t* active,
     return DPG_OK;
 }
 
+/* ---- correlative scan matching: parameters, smoothing table, rotations (the contract is in
+ * include/dpg_slam_c.h) ---- */
+void dpg_csm_params_default(dpg_csm_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->resolution = 0.1f;
+    p->sigma = 0.1f;
+    p->kernel_radius = 3;
+    p->half_cells = 160;
+    p->half_x = 15;
+    p->half_y = 15;
+    p->half_a = 20;
+    p->angle_step = (float)(0.5 * M_PI / 180.0);
+}
+
+int64_t dpg_csm_lds_bytes(const dpg_csm_params* p) {
+    if (!p) return DPG_ERR_ARG;
+    if (!(p->resolution > 0.0f) || !isfinite(p->resolution) || !(p->sigma > 0.0f) || !isfinite(p->sigma) ||
+        !(p->angle_step > 0.0f) || !isfinite(p->angle_step))
+        return DPG_ERR_ARG;
+    if (p->kernel_radius < 0 || p->kernel_radius > 7 || p->half_cells < 0 || p->half_x < 0 || p->half_x > 64 ||
+        p->half_y < 0 || p->half_y > 64 || p->half_a < 0 || p->half_a > 64)
+        return DPG_ERR_ARG;
+    if (p->half_cells > DPG_CSM_LDS_BUDGET) return DPG_ERR_ARG;   /* the product below stays in int64 */
+    const int64_t w = 2 * (int64_t)p->half_cells + 1 + 4 * (int64_t)p->half_x;
+    const int64_t h = 2 * (int64_t)p->half_cells + 1 + 4 * (int64_t)p->half_y;
+    const int64_t bytes = (w * h + 15) / 16 * 16 + DPG_CSM_LDS_FIXED;
+    return bytes <= DPG_CSM_LDS_BUDGET ? bytes : DPG_ERR_ARG;
+}
+
+int dpg_csm_lut(const dpg_csm_params* p, uint8_t* lut_out) {
+    if (!lut_out || dpg_csm_lds_bytes(p) < 0) return DPG_ERR_ARG;
+    const double res = (double)p->resolution, sigma = (double)p->sigma;
+    const int n = p->kernel_radius * p->kernel_radius;
+    for (int d2 = 0; d2 <= n; ++d2)
+        lut_out[d2] = (uint8_t)floor(255.0 * exp(-(double)d2 * res * res / (2.0 * sigma * sigma)) + 0.5);
+    return DPG_OK;
+}
+
+int dpg_csm_rotations(const float guess[6], const dpg_csm_params* p, float* rot_out) {
+    if (!guess || !rot_out || dpg_csm_lds_bytes(p) < 0) return DPG_ERR_ARG;
+    const double tg = atan2((double)guess[3], (double)guess[0]);
+    for (int a = 0; a <= 2 * p->half_a; ++a) {
+        const double ang = tg + (double)(a - p->half_a) * (double)p->angle_step;
+        rot_out[2 * a] = (float)cos(ang);
+        rot_out[2 * a + 1] = (float)sin(ang);
+    }
+    return DPG_OK;
+}
+
 /* R9: odometry BetweenFactor from two odom_only_estimates (dpg_slam.cc:56-75). */
 int dpg_odometry_factor(const float odom_prev[3], const float odom_cur[3], int32_t i_prev, int32_t i_cur,
                         float transl_from_transl, float transl_from_rot, float rot_from_transl,

@@ -257,10 +257,11 @@ static int scans_append_1(dpg_ctx* c, const float* pts, const int64_t* off, int6
 }
 
 // The kernel's edge records of a batch in the caller's order (R3 guesses, dpg_slam.cc:364-378;
-// pad[0] = the caller's index), the kernel scalars and the largest clouds.
-static int build_batch(dpg_ctx* c, const int32_t* edges, int64_t ne, const float* poses, const dpg_icp_params* p,
-                       std::vector<dpg_icp_edge>& out, dpg_icp_kparams& kp, int32_t& ms, int32_t& mt) {
-    if (!c || (!edges && ne > 0) || ne < 0 || !poses || !p) return fail(DPG_ERR_ARG, "dpg_icp_batch_prepare: bad arguments");
+// pad[0] = the caller's index), the kernel scalars and the largest clouds.  guesses ([ne][6]) given:
+// the edges' guesses as they stand, poses unused (dpg_icp_batch_prepare_guess).
+static int build_batch(dpg_ctx* c, const int32_t* edges, int64_t ne, const float* poses, const float* guesses,
+                       const dpg_icp_params* p, std::vector<dpg_icp_edge>& out, dpg_icp_kparams& kp, int32_t& ms, int32_t& mt) {
+    if (!c || (!edges && ne > 0) || ne < 0 || (!poses && !guesses) || !p) return fail(DPG_ERR_ARG, "dpg_icp_batch_prepare: bad arguments");
     if (c->n_nodes <= 0) return fail(DPG_ERR_STATE, "no scans uploaded");
     if (p->downsample_icp_points_ratio != c->ratio && !(p->downsample_icp_points_ratio < 1 && c->ratio == 1))
         return fail(DPG_ERR_STATE, "scans were uploaded with downsample ratio %d", c->ratio);
@@ -284,7 +285,8 @@ static int build_batch(dpg_ctx* c, const int32_t* edges, int64_t ne, const float
         E.n_src_full = (int32_t)(c->full_off[(size_t)s + 1] - c->full_off[(size_t)s]);
         E.tgt_full_off = (int32_t)c->full_off[(size_t)t];
         E.n_tgt_full = (int32_t)(c->full_off[(size_t)t + 1] - c->full_off[(size_t)t]);
-        dpg_icp_guess(poses + 3 * s, poses + 3 * t, E.guess);  // R3 (dpg_slam.cc:364-378)
+        if (guesses) memcpy(E.guess, guesses + 6 * e, sizeof(E.guess));
+        else dpg_icp_guess(poses + 3 * s, poses + 3 * t, E.guess);  // R3 (dpg_slam.cc:364-378)
         E.pad[0] = (int32_t)e;
         ms = std::max(ms, E.n_src_ds);
         mt = std::max(mt, E.n_tgt_ds);
@@ -621,12 +623,13 @@ int dpg_scans_index_all(dpg_ctx* c) {
 
 // Stage an edge batch on every device.  The assignment uses measured costs when every edge of the
 // batch has been aligned before (a sweep re-aligns the previous sweep's pairs from similar guesses).
-int dpg_icp_batch_prepare(dpg_ctx* c, const int32_t* edges, int64_t ne, const float* poses, const dpg_icp_params* p) {
+static int batch_prepare(dpg_ctx* c, const int32_t* edges, int64_t ne, const float* poses, const float* guesses,
+                         const dpg_icp_params* p) {
     if (!c) return fail(DPG_ERR_ARG, "dpg_icp_batch_prepare: bad arguments");
     int32_t ms = 0, mt = 0;
     dpg_icp_kparams kp;
     std::vector<dpg_icp_edge> all;
-    int rc = build_batch(c, edges, ne, poses, p, all, kp, ms, mt);
+    int rc = build_batch(c, edges, ne, poses, guesses, p, all, kp, ms, mt);
     if (rc) return rc;
     c->batch.swap(all);
     c->kp = kp;
@@ -634,6 +637,18 @@ int dpg_icp_batch_prepare(dpg_ctx* c, const int32_t* edges, int64_t ne, const fl
     c->max_tgt = mt;
     c->batch_runs = 0;
     return plan_and_stage(c, c->schedule == DPG_ICP_SCHEDULE_MEASURED && ne > 0 && batch_costs_known(c));
+}
+
+int dpg_icp_batch_prepare(dpg_ctx* c, const int32_t* edges, int64_t ne, const float* poses, const dpg_icp_params* p) {
+    if (!poses) return fail(DPG_ERR_ARG, "dpg_icp_batch_prepare: bad arguments");
+    return batch_prepare(c, edges, ne, poses, nullptr, p);
+}
+
+// the same with every edge's guess given (a scan matcher's refined guesses, dpg_csm_batch)
+int dpg_icp_batch_prepare_guess(dpg_ctx* c, const int32_t* edges, int64_t ne, const float* guesses,
+                                const dpg_icp_params* p) {
+    if (!guesses) return fail(DPG_ERR_ARG, "dpg_icp_batch_prepare_guess: guesses is NULL");
+    return batch_prepare(c, edges, ne, nullptr, guesses, p);
 }
 
 // Run the staged batch on every device (launches only: the devices run concurrently).  A batch

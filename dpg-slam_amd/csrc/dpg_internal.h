@@ -106,6 +106,15 @@ int dpg_launch_icp_ang(const float* ds_pts_dev, const float* idx_pts_dev, const 
 size_t dpg_icp_ang_lds_bytes(int32_t cap);
 size_t dpg_icp_ang_scratch_per_edge(int32_t cap);
 
+/* One pair of the correlative scan matcher as its kernel sees it (dpg_csm.hip; 32 B).  Offsets and
+   counts are in points of the downsampled store. */
+typedef struct dpg_csm_pair {
+    int32_t tgt_off, n_tgt;
+    int32_t src_off, n_src;
+    float tx, ty;                    /* the guess's translation; its rotations are in the pair's table */
+    int32_t pad[2];
+} dpg_csm_pair;
+
 /* Pose-graph system on device (defined in dpg_gn.hip). */
 typedef struct dpg_gn_dev {
     int64_t n_nodes, n_factors, nnzb_upper, nnzb_full;

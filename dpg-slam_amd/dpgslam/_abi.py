@@ -241,6 +241,30 @@ class GridInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class CsmParams(C.Structure):
+    """dpg_csm_params -- raster, smoothing and search window of the correlative scan matcher."""
+
+    _fields_ = [("resolution", C.c_float), ("sigma", C.c_float), ("kernel_radius", C.c_int32),
+                ("half_cells", C.c_int32), ("half_x", C.c_int32), ("half_y", C.c_int32), ("half_a", C.c_int32),
+                ("angle_step", C.c_float)]
+
+
+class CsmResult(C.Structure):
+    """dpg_csm_result -- the refined guess of one pair, its score and where in the window it lies."""
+
+    _fields_ = [("guess", C.c_float * 6), ("score", C.c_int32), ("score_at_guess", C.c_int32), ("n_src", C.c_int32),
+                ("best_a", C.c_int32), ("best_dx", C.c_int32), ("best_dy", C.c_int32), ("status", C.c_int32),
+                ("pad", C.c_int32 * 3)]
+
+
+CSM_RESULT_DTYPE = np.dtype(
+    [("guess", "<f4", (6,)), ("score", "<i4"), ("score_at_guess", "<i4"), ("n_src", "<i4"), ("best_a", "<i4"),
+     ("best_dx", "<i4"), ("best_dy", "<i4"), ("status", "<i4"), ("pad", "<i4", (3,))], align=True)
+assert CSM_RESULT_DTYPE.itemsize == C.sizeof(CsmResult) == 64 and C.sizeof(CsmParams) == 32
+DPG_CSM_OK = 0
+DPG_CSM_NO_OVERLAP = 1
+
+
 ALLREDUCE_F64 = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int64)
 ALLREDUCE_F32 = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_float), C.c_int64)
 ALLGATHER = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
@@ -357,6 +381,15 @@ SIGNATURES = {
     "dpg_dpg_beam_geometry": (C.c_int, [P, C.c_int64, F32P, F32P, F32P, C.c_int64]),
     "dpg_occupancy_from_counts": (None, [I32P, I32P, C.c_int64, I8P]),
     "dpg_grid_box": (C.c_int, [F32P, F32P, U8P, C.c_int64, C.c_double, C.c_int32, I32P]),
+    "dpg_csm_params_default": (None, [C.POINTER(CsmParams)]),
+    "dpg_csm_lds_bytes": (C.c_int64, [C.POINTER(CsmParams)]),
+    "dpg_csm_lut": (C.c_int, [C.POINTER(CsmParams), U8P]),
+    "dpg_csm_rotations": (C.c_int, [F32P, C.POINTER(CsmParams), F32P]),
+    "dpg_csm_batch": (C.c_int, [P, I32P, C.c_int64, F32P, F32P, C.POINTER(CsmParams), P, C.c_int64]),
+    "dpg_csm_table": (C.c_int, [P, C.c_int32, C.POINTER(CsmParams), U8P, C.c_int64]),
+    "dpg_csm_scores": (C.c_int, [P, C.c_int32, C.c_int32, F32P, C.POINTER(CsmParams), I32P, C.c_int64]),
+    "dpg_csm_kernel_ms": (C.c_float, [P]),
+    "dpg_icp_batch_prepare_guess": (C.c_int, [P, I32P, C.c_int64, F32P, C.POINTER(IcpParams)]),
     "dpg_reoptimize": (C.c_int, [P, C.c_int64, I32P, F32P, F32P, C.POINTER(IcpParams), C.POINTER(GnParams),
                                  C.POINTER(ReoptParams), F64P, C.POINTER(ReoptStats)]),
     "dpg_reoptimize_inc": (C.c_int, [P, C.c_int64, I32P, F32P, F32P, C.POINTER(IcpParams), C.POINTER(ReoptParams),
@@ -468,6 +501,12 @@ default_change_params_host = default_change_params
 def default_grid_params() -> GridParams:
     p = GridParams()
     lib().dpg_grid_params_default(C.byref(p))
+    return p
+
+
+def default_csm_params() -> CsmParams:
+    p = CsmParams()
+    lib().dpg_csm_params_default(C.byref(p))
     return p
 
 

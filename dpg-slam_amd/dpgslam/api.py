@@ -121,6 +121,33 @@ def icp_guess(pose_src, pose_tgt) -> np.ndarray:
     return o
 
 
+def csm_lut(params=None) -> np.ndarray:
+    """dpg_csm_lut (host): the scan matcher's smoothing bytes by squared cell distance, uint8 [R * R + 1]."""
+    p = params or _abi.default_csm_params()
+    out = np.zeros(max(int(p.kernel_radius), 0) ** 2 + 1, np.uint8)
+    check(lib().dpg_csm_lut(C.byref(p), ptr(out, C.c_uint8)), "dpg_csm_lut")
+    return out
+
+
+def csm_rotations(guess, params=None) -> np.ndarray:
+    """dpg_csm_rotations (host): (cos, sin) of every angle of the window around the guess, float32 [2 half_a + 1, 2]."""
+    p = params or _abi.default_csm_params()
+    g = _f32(guess).reshape(6)
+    out = np.zeros((2 * max(int(p.half_a), 0) + 1, 2), np.float32)
+    check(lib().dpg_csm_rotations(ptr(g, C.c_float), C.byref(p), ptr(out, C.c_float)), "dpg_csm_rotations")
+    return out
+
+
+def csm_lds_bytes(params=None) -> int:
+    """dpg_csm_lds_bytes (host): the matcher kernel's LDS working set; raises for invalid params or
+    a table and window above the budget."""
+    p = params or _abi.default_csm_params()
+    n = int(lib().dpg_csm_lds_bytes(C.byref(p)))
+    if n < 0:
+        raise _abi.DpgError(f"dpg_csm_lds_bytes failed ({n}): invalid parameters or above the LDS budget")
+    return n
+
+
 def odometry_factor(odom_prev, odom_cur, i_prev, i_cur, motion=(0.4, 0.4, 0.4, 0.4)):
     a, b = _f32(odom_prev), _f32(odom_cur)
     f = _abi.Factor()
@@ -401,6 +428,62 @@ class Context:
         self.icp_prepare(edges, poses, params)
         self.icp_run(compute_cov, trace_iters)
         return self.icp_fetch(compute_cov)
+
+    def icp_prepare_guess(self, edges: np.ndarray, guesses: np.ndarray, params=None):
+        """icp_prepare with every edge's guess given ([E, 6], rows as dpg_icp_guess writes them) instead
+        of derived from poses (dpg_icp_batch_prepare_guess); icp_run / icp_fetch follow unchanged."""
+        p = params or _abi.default_icp_params()
+        e = np.ascontiguousarray(edges, np.int32).reshape(-1, 2)
+        g = _f32(guesses).reshape(-1, 6)
+        if len(g) != len(e):
+            raise ValueError(f"icp_prepare_guess: {len(e)} edges but {len(g)} guesses")
+        check(lib().dpg_icp_batch_prepare_guess(self.handle, ptr(e, C.c_int32), len(e), ptr(g, C.c_float), C.byref(p)),
+              "dpg_icp_batch_prepare_guess")
+        self.n_edges = len(e)
+
+    def icp_batch_guess(self, edges, guesses, params=None, compute_cov=True, trace_iters=0):
+        """icp_batch from explicit guesses."""
+        self.icp_prepare_guess(edges, guesses, params)
+        self.icp_run(compute_cov, trace_iters)
+        return self.icp_fetch(compute_cov)
+
+    # ---- correlative scan matching (a guess for ICP that needs no good guess) ----
+    def csm_batch(self, edges, poses=None, guesses=None, params=None) -> np.ndarray:
+        """dpg_csm_batch over the uploaded scans: per edge (target, source) the best pose of the
+        window around the guess -- poses [V, 3] (turned into guesses as icp_prepare does) or guesses
+        [E, 6], exactly one of them.  Returns a structured array (_abi.CSM_RESULT_DTYPE): the refined
+        guess, score, score_at_guess, n_src, best_a, best_dx, best_dy, status."""
+        p = params or _abi.default_csm_params()
+        e = np.ascontiguousarray(edges, np.int32).reshape(-1, 2)
+        ps = None if poses is None else _f32(poses).reshape(-1, 3)
+        g = None if guesses is None else _f32(guesses).reshape(-1, 6)
+        if g is not None and len(g) != len(e):
+            raise ValueError(f"csm_batch: {len(e)} edges but {len(g)} guesses")
+        out = np.zeros(len(e), _abi.CSM_RESULT_DTYPE)
+        check(lib().dpg_csm_batch(self.handle, ptr(e, C.c_int32), len(e), ptr(ps, C.c_float), ptr(g, C.c_float),
+                                  C.byref(p), vptr(out), len(out)), "dpg_csm_batch")
+        return out
+
+    def csm_table(self, node: int, params=None) -> np.ndarray:
+        """Diagnostic: the smoothed table of one node as the kernel built it, uint8
+        [2 half_cells + 1, 2 half_cells + 1], row v, column u."""
+        p = params or _abi.default_csm_params()
+        w = 2 * max(int(p.half_cells), 0) + 1
+        out = np.zeros((w, w), np.uint8)
+        check(lib().dpg_csm_table(self.handle, int(node), C.byref(p), ptr(out, C.c_uint8), out.size), "dpg_csm_table")
+        return out
+
+    def csm_scores(self, target: int, source: int, guess, params=None) -> np.ndarray:
+        """Diagnostic: the full score volume of one pair, int32 [2 half_a + 1, 2 half_y + 1, 2 half_x + 1]."""
+        p = params or _abi.default_csm_params()
+        g = _f32(guess).reshape(6)
+        out = np.zeros((2 * max(int(p.half_a), 0) + 1, 2 * max(int(p.half_y), 0) + 1, 2 * max(int(p.half_x), 0) + 1), np.int32)
+        check(lib().dpg_csm_scores(self.handle, int(target), int(source), ptr(g, C.c_float), C.byref(p),
+                                   ptr(out, C.c_int32), out.size), "dpg_csm_scores")
+        return out
+
+    def csm_kernel_ms(self) -> float:
+        return float(lib().dpg_csm_kernel_ms(self.handle))
 
     def icp_kernel_ms(self) -> float:
         return float(lib().dpg_icp_batch_kernel_ms(self.handle))

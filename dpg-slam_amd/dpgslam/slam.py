@@ -61,11 +61,25 @@ class GpuBackend:
     def icp_batch(self, clouds, edges, est, p):
         """clouds() -> (pts, offsets) of every node; the store already holds them when every node
         came through add_node."""
-        if self.stored != len(est):
-            pts, offsets = clouds()
-            self.ctx.upload_scans(pts, offsets, p.downsample_icp_points_ratio)
-            self.stored = len(est)
+        self._ensure_scans(clouds, len(est), p.downsample_icp_points_ratio)
         res, _ = self.ctx.icp_batch(edges, est, p, compute_cov=False)
+        return res
+
+    def _ensure_scans(self, clouds, n_nodes, ratio):
+        if self.stored != n_nodes:
+            pts, offsets = clouds()
+            self.ctx.upload_scans(pts, offsets, ratio)
+            self.stored = n_nodes
+
+    def prematch(self, clouds, edges, est, csm_params, ratio):
+        """The correlative scan match of `edges` from the estimates (dpg_csm_batch)."""
+        self._ensure_scans(clouds, len(est), ratio)
+        return self.ctx.csm_batch(edges, poses=est, params=csm_params)
+
+    def icp_batch_guess(self, clouds, edges, guesses, n_nodes, p):
+        """icp_batch with every edge's guess given."""
+        self._ensure_scans(clouds, n_nodes, p.downsample_icp_points_ratio)
+        res, _ = self.ctx.icp_batch_guess(edges, guesses, p, compute_cov=False)
         return res
 
     def candidates(self, est, passes, within, across):
@@ -90,10 +104,7 @@ class GpuBackend:
         return api.DpgStore(self.ctx, ranges, geom, offsets=offsets, params=params)
 
     def get_map(self, clouds, est, fraction, ratio):
-        if self.stored != len(est):
-            pts, offsets = clouds()
-            self.ctx.upload_scans(pts, offsets, ratio)
-            self.stored = len(est)
+        self._ensure_scans(clouds, len(est), ratio)
         return self.ctx.get_map(est, fraction)
 
 
@@ -105,7 +116,17 @@ class DpgSLAM:
                  change_params=None, min_dist_between_nodes=1.0, min_angle_between_nodes=math.pi / 6.0,
                  non_successive_scan_constraints=True, odometry_constraints=True,
                  max_dist_within_pass=5.0, max_dist_across_passes=2.0, new_pass_std_dev=(0.2, 0.2, 0.15),
-                 motion_model=(0.4, 0.4, 0.4, 0.4), display_points_fraction=10, inc_mode="isam2"):
+                 motion_model=(0.4, 0.4, 0.4, 0.4), display_points_fraction=10, inc_mode="isam2",
+                 loop_closure_prematch=None, prematch_min_response=0.0):
+        """loop_closure_prematch: None (the reference's behaviour), or a _abi.CsmParams: reoptimize()
+        then runs the correlative scan matcher (dpg_csm_batch) on its loop-closure candidates -- not
+        on the successive pairs -- and starts the ICP of a candidate from the matcher's pose where
+        score / (255 n_src) >= prematch_min_response, so that a candidate whose estimates drifted
+        beyond ICP's correspondence distance can still close.  The per-node path (dpg_add_node, one C
+        call per node) is out of scope: it aligns from the estimates as before."""
+        self.prematch_params = loop_closure_prematch
+        self.prematch_min_response = float(prematch_min_response)
+        self.last_prematch = None                       # the matcher's records of the last sweep
         if backend == "gpu":
             self.ctx = ctx or api.Context(0)
             self.be = GpuBackend(self.ctx, inc_mode)
@@ -266,7 +287,9 @@ class DpgSLAM:
         succ = np.stack([np.arange(V - 1), np.arange(1, V)], 1).astype(np.int32)
         edges = np.concatenate([succ, np.asarray(lc, np.int32).reshape(-1, 2)], 0)
         res = None
-        if len(edges):
+        if len(edges) and self.prematch_params is not None:
+            res = self._icp_batch_prematched(edges, len(succ), est)
+        elif len(edges):
             res = self.be.icp_batch(self._clouds, edges, est, self.icp_params)
         t2 = time.perf_counter()
         # per node, in node order: the pass's prior on its first node, else the odometry Between
@@ -309,6 +332,25 @@ class DpgSLAM:
                                       gn_iterations=int(st.gn_iterations))
 
     # ------------------------------------------------------------------ internals
+    def _icp_batch_prematched(self, edges, n_succ, est):
+        """The sweep's alignments with loop_closure_prematch on: every edge's guess is
+        dpg_icp_guess's, except the loop-closure candidates (edges[n_succ:]) the matcher answered
+        with a response of at least prematch_min_response, which start from its refined guess."""
+        for name in ("prematch", "icp_batch_guess"):
+            if getattr(self.be, name, None) is None:
+                raise NotImplementedError(f"loop_closure_prematch needs a `{name}` method on the backend; "
+                                          f"{type(self.be).__name__} has none")
+        guesses = np.stack([api.icp_guess(est[s], est[t]) for t, s in edges]).astype(f32)
+        self.last_prematch = None
+        if len(edges) > n_succ:
+            m = self.be.prematch(self._clouds, edges[n_succ:], est, self.prematch_params,
+                                 self.icp_params.downsample_icp_points_ratio)
+            response = m["score"] / (255.0 * np.maximum(m["n_src"], 1))
+            take = response >= self.prematch_min_response
+            guesses[n_succ:][take] = m["guess"][take]
+            self.last_prematch = m
+        return self.be.icp_batch_guess(self._clouds, edges, guesses, len(est), self.icp_params)
+
     def _odometry_factor(self, prev, cur, i, j):
         f = api.odometry_factor(prev, cur, i, j, self.motion)
         return np.frombuffer(bytes(f), FACTOR_DTYPE).copy()

@@ -822,6 +822,103 @@ void dpg_occupancy_from_counts(const int32_t* hits, const int32_t* misses, int64
 int dpg_grid_box(const float* lidar_xy, const float* r_v, const uint8_t* active, int64_t n, double res,
                  int32_t margin, int32_t box[4]);
 
+/* ---- correlative scan matching: a loop-closure guess that needs no good guess ----
+ * Every alignment starts ICP from the pose estimates (dpg_icp_guess) and ICP's correspondence search
+ * stops at icp_max_correspondence_distance, so a loop-closure candidate whose estimates drifted by
+ * more than about that much fails its ICP.  dpg_csm_batch scores, per pair (target t, source s),
+ * every pose in a window of (dx, dy, dtheta) around the guess against a smoothed raster of the target
+ * scan (Olson 2009) and returns the best pose as the refined guess, which dpg_icp_batch_prepare_guess
+ * hands to ICP.  The reference has no such stage.  After one float transform per point and angle all
+ * work is integer, so every output is exact and order-free.
+ *
+ *   lut[d2], 0 <= d2 <= R^2 (R = kernel_radius): (uint8)floor(255 exp(-d2 res^2 / (2 sigma^2)) + 0.5),
+ *     in double, res and sigma widened from float.  Non-increasing in d2.
+ *   key of a coordinate v (float): round((double)v / res), C round, res widened from float -- the
+ *     occupancy grid's rule.  A point with a non-finite coordinate or |(double)v / res| >= 2^29
+ *     contributes nothing, as target and as source.
+ *   Table T of node t, cell keys (u, v) in [-half_cells, half_cells]^2, in t's own frame, over the
+ *     store's downsampled cloud of t: T[u, v] = max of lut[d2] over the target points whose key lies
+ *     at squared cell distance d2 <= R^2 from (u, v); 0 when there is none.  A point whose own key lies
+ *     outside the table still spreads into it.
+ *   Rotations (dpg_csm_rotations): theta_g = atan2((double)guess[3], (double)guess[0]),
+ *     angle_a = theta_g + (a - half_a) (double)angle_step, (c_a, s_a) = ((float)cos, (float)sin) of it,
+ *     a = 0 .. 2 half_a.  The kernel receives this table and calls no trigonometric function.
+ *   Source cell of point (x, y) at angle a, with (tx, ty) = (guess[2], guess[5]), in float, one
+ *     rounding per operation: qx = ((c_a x) - (s_a y)) + tx, qy = ((s_a x) + (c_a y)) + ty;
+ *     (kx, ky) = the keys of (qx, qy).
+ *   score(a, dx, dy), |dx| <= half_x, |dy| <= half_y: the int32 sum over the source points of
+ *     T[kx + dx, ky + dy], over the points whose shifted cell lies in the table.
+ *   Winner: the highest score; ties by smaller |a - half_a|, then smaller dx^2 + dy^2, then smaller a,
+ *     then smaller dy, then smaller dx.
+ *   Refined guess rows: (c_a, -s_a, (float)((double)tx + dx (double)res)),
+ *                       (s_a,  c_a, (float)((double)ty + dy (double)res)).
+ * One workgroup per pair with the table in LDS.  Its working set must fit 160 KiB:
+ *   dpg_csm_lds_bytes = round_up_16((2 half_cells + 1 + 4 half_x) (2 half_cells + 1 + 4 half_y))
+ *                       + DPG_CSM_LDS_FIXED <= DPG_CSM_LDS_BUDGET
+ * (the table with a zero apron of twice the window on every side, then a fixed part: one chunk of
+ * packed source cells, the smoothing stencil, the reduction words). */
+typedef struct dpg_csm_params {
+    float resolution;       /* m per cell, default 0.1; finite, > 0 */
+    float sigma;            /* smoothing, m, default 0.1; finite, > 0 */
+    int32_t kernel_radius;  /* R, cells, default 3; 0 .. 7 */
+    int32_t half_cells;     /* default 160; the table covers keys [-half_cells, half_cells]^2; >= 0 */
+    int32_t half_x, half_y; /* translation window, cells, default 15, 15; 0 .. 64 */
+    int32_t half_a;         /* angle window, steps, default 20; 0 .. 64 */
+    float angle_step;       /* radians per step, default 0.5 degrees; finite, > 0 */
+} dpg_csm_params;
+
+#define DPG_CSM_OK 0
+#define DPG_CSM_NO_OVERLAP 1   /* the best score is 0: no source point met the table anywhere in the window */
+typedef struct dpg_csm_result {
+    float guess[6];         /* the refined guess, rows as dpg_icp_guess writes them */
+    int32_t score;          /* the winner's score */
+    int32_t score_at_guess; /* score(half_a, 0, 0) */
+    int32_t n_src;          /* points of the source cloud: the largest possible score is 255 n_src */
+    int32_t best_a, best_dx, best_dy;   /* the winner: a in 0 .. 2 half_a, dx, dy in cells */
+    int32_t status;         /* DPG_CSM_* */
+    int32_t pad[3];
+} dpg_csm_result;
+
+#define DPG_CSM_PARAMS_SIZE 32
+#define DPG_CSM_RESULT_SIZE 64
+#define DPG_CSM_LDS_FIXED 9536
+#define DPG_CSM_LDS_BUDGET 163840
+#ifdef __cplusplus
+ static_assert(sizeof(dpg_csm_params) == DPG_CSM_PARAMS_SIZE && sizeof(dpg_csm_result) == DPG_CSM_RESULT_SIZE, "csm ABI structs");
+#else
+ _Static_assert(sizeof(dpg_csm_params) == DPG_CSM_PARAMS_SIZE && sizeof(dpg_csm_result) == DPG_CSM_RESULT_SIZE, "csm ABI structs");
+#endif
+
+void dpg_csm_params_default(dpg_csm_params* p);
+/* Host.  The kernel's LDS bytes by the formula above; DPG_ERR_ARG for an invalid field or a working
+ * set above DPG_CSM_LDS_BUDGET (every dpg_csm_* call checks its params through this). */
+int64_t dpg_csm_lds_bytes(const dpg_csm_params* p);
+/* Host.  lut_out[R * R + 1]; for the defaults 255, 155, 94, 57, 35, 21, 13, 8, 5, 3. */
+int dpg_csm_lut(const dpg_csm_params* p, uint8_t* lut_out);
+/* Host.  rot_out[2 half_a + 1][2] = (c_a, s_a). */
+int dpg_csm_rotations(const float guess[6], const dpg_csm_params* p, float* rot_out);
+/* The match of n_edges pairs, edges[e] = {target, source} over the uploaded scan store, on the context
+ * stream; blocks until results_out[n_edges] is written.  Exactly one of poses ([V][3], turned into
+ * guesses by dpg_icp_guess as dpg_icp_batch_prepare does) and guesses ([n_edges][6]) is given.
+ * Errors: DPG_ERR_ARG -- params, an edge naming a missing node, both or neither of poses / guesses;
+ * DPG_ERR_STATE -- no scans uploaded, or a multi-device, virtual or rank context; DPG_ERR_SIZE, with
+ * nothing written -- cap < n_edges. */
+int dpg_csm_batch(dpg_ctx* ctx, const int32_t* edges, int64_t n_edges, const float* poses, const float* guesses,
+                  const dpg_csm_params* params, dpg_csm_result* results_out, int64_t cap);
+/* Diagnostic: the table of one node as the kernel built it, (2 half_cells + 1)^2 bytes, row-major
+ * with v outer; cap in bytes, DPG_ERR_SIZE when smaller. */
+int dpg_csm_table(dpg_ctx* ctx, int32_t node, const dpg_csm_params* params, uint8_t* out, int64_t cap);
+/* Diagnostic: the full score volume of one pair from the same kernel, out[2 half_a + 1][2 half_y + 1]
+ * [2 half_x + 1]; cap in int32 elements, DPG_ERR_SIZE when smaller. */
+int dpg_csm_scores(dpg_ctx* ctx, int32_t target, int32_t source, const float guess[6], const dpg_csm_params* params,
+                   int32_t* out, int64_t cap);
+/* Device time of the last dpg_csm_batch / _table / _scores kernel (ms, HIP events); < 0 before one. */
+float dpg_csm_kernel_ms(dpg_ctx* ctx);
+/* dpg_icp_batch_prepare with the guess of every edge given (guesses[n_edges][6], rows as
+ * dpg_icp_guess writes them) instead of derived from poses; dpg_icp_batch_run / _fetch follow unchanged. */
+int dpg_icp_batch_prepare_guess(dpg_ctx* ctx, const int32_t* edges, int64_t n_edges, const float* guesses,
+                                const dpg_icp_params* params);
+
 #ifdef __cplusplus
 }
 #endif
