@@ -725,9 +725,18 @@ struct dpg_dpg {
     DevBuf<int8_t> d_occ_out;
     DevBuf<OccCtl> d_occ_ctl;
     DevBuf<float2> d_geo;                     // [lidar positions | end points]
+    DpgLoc loc;                               // dpg_map_localize's field and search buffers (dpg_loc.hip)
     PinBuf<Ctl> h_ctl;
     DevEvent ev[2];
 };
+
+void dpg_dpg_loc_view(dpg_dpg* d, DpgLocView* v) {
+    v->ctx = d->ctx;
+    v->stream = d->s;
+    v->device = d->device;
+    v->occ = d->d_occ_out.p;
+    v->loc = &d->loc;
+}
 
 #define DTRY(expr)                                                                     \
     do {                                                                               \

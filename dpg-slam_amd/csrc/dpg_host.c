@@ -215,6 +215,46 @@ int dpg_csm_rotations(const float guess[6], const dpg_csm_params* p, float* rot_
     return DPG_OK;
 }
 
+/* ---- localisation in the active map: parameters and rotations (the contract is in
+ * include/dpg_slam_c.h) ---- */
+void dpg_loc_params_default(dpg_loc_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->margin_cells = 1;
+    p->sigma = 0.1f;
+    p->kernel_radius = 3;
+    p->occupied_min = 50;
+    p->half_x = 40;
+    p->half_y = 40;
+    p->half_a = 360;
+    p->angle_step = (float)(0.5 * M_PI / 180.0);
+    p->coarse_shift = 4;
+    p->max_refine_blocks = 16384;
+}
+
+int dpg_loc_params_check(const dpg_loc_params* p) {
+    if (!p) return DPG_ERR_ARG;
+    if (!(p->resolution >= 0.0) || !isfinite(p->resolution) || !(p->sigma > 0.0f) || !isfinite(p->sigma) ||
+        !(p->angle_step > 0.0f) || !isfinite(p->angle_step))
+        return DPG_ERR_ARG;
+    if (p->max_cells < 0 || p->max_cells > (int64_t)1 << 25 || p->margin_cells < 0) return DPG_ERR_ARG;
+    if (p->kernel_radius < 0 || p->kernel_radius > 7 || p->occupied_min < 1 || p->occupied_min > 100) return DPG_ERR_ARG;
+    if (p->half_x < 0 || p->half_x > 32768 || p->half_y < 0 || p->half_y > 32768 || p->half_a < 0 || p->half_a > 1024)
+        return DPG_ERR_ARG;
+    if (p->coarse_shift < 0 || p->coarse_shift > 5 || p->max_refine_blocks < 1) return DPG_ERR_ARG;
+    return DPG_OK;
+}
+
+int dpg_loc_rotations(float guess_theta, const dpg_loc_params* p, float* rot_out) {
+    if (!rot_out || dpg_loc_params_check(p)) return DPG_ERR_ARG;
+    for (int a = 0; a <= 2 * p->half_a; ++a) {
+        const double ang = (double)guess_theta + (double)(a - p->half_a) * (double)p->angle_step;
+        rot_out[2 * a] = (float)cos(ang);
+        rot_out[2 * a + 1] = (float)sin(ang);
+    }
+    return DPG_OK;
+}
+
 /* R9: odometry BetweenFactor from two odom_only_estimates (dpg_slam.cc:56-75). */
 int dpg_odometry_factor(const float odom_prev[3], const float odom_cur[3], int32_t i_prev, int32_t i_cur,
                         float transl_from_transl, float transl_from_rot, float rot_from_transl,

@@ -265,6 +265,38 @@ DPG_CSM_OK = 0
 DPG_CSM_NO_OVERLAP = 1
 
 
+class LocParams(C.Structure):
+    """dpg_loc_params -- field, window and pruning of the localisation in the active map."""
+
+    _fields_ = [("resolution", C.c_double), ("max_cells", C.c_int64), ("margin_cells", C.c_int32), ("sigma", C.c_float),
+                ("kernel_radius", C.c_int32), ("occupied_min", C.c_int32), ("half_x", C.c_int32), ("half_y", C.c_int32),
+                ("half_a", C.c_int32), ("angle_step", C.c_float), ("coarse_shift", C.c_int32),
+                ("max_refine_blocks", C.c_int32)]
+
+
+class LocResult(C.Structure):
+    """dpg_loc_result -- the pose of one scan in the active map and how the search found it."""
+
+    _fields_ = [("pose", C.c_float * 3), ("rot", C.c_float * 2), ("score", C.c_int32), ("score_at_guess", C.c_int32),
+                ("n_pts", C.c_int32), ("best_a", C.c_int32), ("best_dx", C.c_int32), ("best_dy", C.c_int32),
+                ("status", C.c_int32), ("n_seeds", C.c_int32), ("box", C.c_int32 * 4), ("pad", C.c_int32),
+                ("n_blocks", C.c_int64), ("n_frontier", C.c_int64), ("n_refined_candidates", C.c_int64),
+                ("ms_kernels", C.c_double), ("ms_field", C.c_double), ("ms_bound", C.c_double), ("ms_fine", C.c_double)]
+
+
+LOC_RESULT_DTYPE = np.dtype(
+    [("pose", "<f4", (3,)), ("rot", "<f4", (2,)), ("score", "<i4"), ("score_at_guess", "<i4"), ("n_pts", "<i4"),
+     ("best_a", "<i4"), ("best_dx", "<i4"), ("best_dy", "<i4"), ("status", "<i4"), ("n_seeds", "<i4"),
+     ("box", "<i4", (4,)), ("pad", "<i4"), ("n_blocks", "<i8"), ("n_frontier", "<i8"), ("n_refined_candidates", "<i8"),
+     ("ms_kernels", "<f8"), ("ms_field", "<f8"), ("ms_bound", "<f8"), ("ms_fine", "<f8")], align=True)
+assert LOC_RESULT_DTYPE.itemsize == C.sizeof(LocResult) == 128 and C.sizeof(LocParams) == 56
+# the fields of a record that two runs of one request share (everything but the timings)
+LOC_RESULT_EXACT = tuple(n for n in LOC_RESULT_DTYPE.names if not n.startswith("ms_"))
+DPG_LOC_OK = 0
+DPG_LOC_NO_OVERLAP = 1
+DPG_LOC_UNPROVEN = 2
+
+
 ALLREDUCE_F64 = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int64)
 ALLREDUCE_F32 = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_float), C.c_int64)
 ALLGATHER = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
@@ -390,6 +422,16 @@ SIGNATURES = {
     "dpg_csm_scores": (C.c_int, [P, C.c_int32, C.c_int32, F32P, C.POINTER(CsmParams), I32P, C.c_int64]),
     "dpg_csm_kernel_ms": (C.c_float, [P]),
     "dpg_icp_batch_prepare_guess": (C.c_int, [P, I32P, C.c_int64, F32P, C.POINTER(IcpParams)]),
+    "dpg_loc_params_default": (None, [C.POINTER(LocParams)]),
+    "dpg_loc_params_check": (C.c_int, [C.POINTER(LocParams)]),
+    "dpg_loc_rotations": (C.c_int, [C.c_float, C.POINTER(LocParams), F32P]),
+    "dpg_map_localize": (C.c_int, [P, C.c_int64, F32P, F32P, C.c_int64, F32P, C.POINTER(LocParams),
+                                   C.POINTER(LocResult)]),
+    "dpg_map_field": (C.c_int, [P, C.c_int64, F32P, C.POINTER(LocParams), C.c_int32, U8P, C.c_int64, I32P]),
+    "dpg_map_localize_bounds": (C.c_int, [P, C.c_int64, F32P, F32P, C.c_int64, F32P, C.POINTER(LocParams), I32P,
+                                          C.c_int64]),
+    "dpg_map_localize_scores": (C.c_int, [P, C.c_int64, F32P, F32P, C.c_int64, F32P, C.POINTER(LocParams), I32P,
+                                          C.c_int64]),
     "dpg_reoptimize": (C.c_int, [P, C.c_int64, I32P, F32P, F32P, C.POINTER(IcpParams), C.POINTER(GnParams),
                                  C.POINTER(ReoptParams), F64P, C.POINTER(ReoptStats)]),
     "dpg_reoptimize_inc": (C.c_int, [P, C.c_int64, I32P, F32P, F32P, C.POINTER(IcpParams), C.POINTER(ReoptParams),
@@ -507,6 +549,12 @@ def default_grid_params() -> GridParams:
 def default_csm_params() -> CsmParams:
     p = CsmParams()
     lib().dpg_csm_params_default(C.byref(p))
+    return p
+
+
+def default_loc_params() -> LocParams:
+    p = LocParams()
+    lib().dpg_loc_params_default(C.byref(p))
     return p
 
 

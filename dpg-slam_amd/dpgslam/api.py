@@ -138,6 +138,19 @@ def csm_rotations(guess, params=None) -> np.ndarray:
     return out
 
 
+def loc_rotations(guess_theta, params=None) -> np.ndarray:
+    """dpg_loc_rotations (host): (cos, sin) of every angle of the localisation's window, float32 [2 half_a + 1, 2]."""
+    p = params or _abi.default_loc_params()
+    out = np.zeros((2 * min(max(int(p.half_a), 0), 1024) + 1, 2), np.float32)
+    check(lib().dpg_loc_rotations(float(np.float32(guess_theta)), C.byref(p), ptr(out, C.c_float)), "dpg_loc_rotations")
+    return out
+
+
+def loc_params_valid(params) -> bool:
+    """dpg_loc_params_check (host): every field inside its range."""
+    return lib().dpg_loc_params_check(C.byref(params)) == _abi.DPG_OK
+
+
 def csm_lds_bytes(params=None) -> int:
     """dpg_csm_lds_bytes (host): the matcher kernel's LDS working set; raises for invalid params or
     a table and window above the budget."""
@@ -821,6 +834,82 @@ class DpgStore:
                "data": data}
         if counts:
             out.update(hits=hits, misses=misses, info=info)
+        return out
+
+    # ---- localisation of one scan in the active map (dpg_map_localize; the contract is in dpg_slam_c.h)
+    def _loc_args(self, est, cloud, guess, params):
+        e = _f32(est).reshape(-1, 3)
+        c = _f32(cloud).reshape(-1, 2)
+        g = _f32(guess).reshape(3)
+        return e, c, g, params or _abi.default_loc_params()
+
+    def map_window(self, n_nodes: int, est, params=None):
+        """(guess_x, guess_y, half_x, half_y): the window that covers the field's whole box, centred on
+        it, from the planning form of dpg_occupancy_grid.  A scan that lies in the map has its pose in
+        the box, so this window holds it."""
+        p = params or _abi.default_loc_params()
+        gp = _abi.default_grid_params()
+        gp.resolution, gp.max_cells, gp.margin_cells = p.resolution, p.max_cells, p.margin_cells
+        info = _abi.GridInfo()
+        e = _f32(est).reshape(-1, 3)
+        check(lib().dpg_occupancy_grid(self.handle, n_nodes, ptr(e, C.c_float), C.byref(gp), None, None, None, 0,
+                                       C.byref(info)), "dpg_occupancy_grid")
+        res = float(info.resolution)
+        cx, cy = info.x0 + info.w // 2, info.y0 + info.h // 2
+        return cx * res, cy * res, min(info.w // 2 + 1, 32768), min(info.h // 2 + 1, 32768)
+
+    def localize(self, n_nodes: int, est, cloud, guess=(0.0, 0.0, 0.0), params=None, window=None):
+        """The pose of `cloud` ([n, 2], body frame) in the active map of nodes [0, n_nodes) at est
+        (dpg_map_localize): a LOC_RESULT_DTYPE record.  window="map" centres the translation window on
+        the field's box and makes it cover the box (guess keeps its theta); None takes guess and
+        half_x / half_y as given."""
+        e, c, g, p = self._loc_args(est, cloud, guess, params)
+        if window == "map":
+            q = _abi.LocParams.from_buffer_copy(bytes(p))
+            gx, gy, q.half_x, q.half_y = self.map_window(n_nodes, e, p)
+            g = _f32([gx, gy, g[2]])
+            p = q
+        elif window is not None:
+            raise ValueError(f"localize: window must be None or 'map', got {window!r}")
+        r = _abi.LocResult()
+        check(lib().dpg_map_localize(self.handle, n_nodes, ptr(e, C.c_float), ptr(c, C.c_float), len(c), ptr(g, C.c_float),
+                                     C.byref(p), C.byref(r)), "dpg_map_localize")
+        return np.frombuffer(bytes(r), _abi.LOC_RESULT_DTYPE)[0].copy()
+
+    def map_field(self, n_nodes: int, est, params=None, shift=-1):
+        """(field, box): the likelihood field F (shift < 0, uint8 [h, w]) or its pooled form P at
+        `shift` (uint8 [h + s - 1, w + s - 1]) as the device built it, and the box (x0, y0, w, h)."""
+        e = _f32(est).reshape(-1, 3)
+        p = params or _abi.default_loc_params()
+        box = np.zeros(4, np.int32)
+        check(lib().dpg_map_field(self.handle, n_nodes, ptr(e, C.c_float), C.byref(p), int(shift), None, 0,
+                                  ptr(box, C.c_int32)), "dpg_map_field")
+        w, h = int(box[2]), int(box[3])
+        s = (1 << shift) if shift > 0 else 1
+        shape = (h + s - 1, w + s - 1) if w * h else (0, 0)
+        out = np.zeros(shape, np.uint8)
+        check(lib().dpg_map_field(self.handle, n_nodes, ptr(e, C.c_float), C.byref(p), int(shift), ptr(out, C.c_uint8),
+                                  out.size, ptr(box, C.c_int32)), "dpg_map_field")
+        return out, tuple(int(b) for b in box)
+
+    def localize_bounds(self, n_nodes: int, est, cloud, guess=(0.0, 0.0, 0.0), params=None):
+        """The bound volume of one request, int32 [2 half_a + 1, nby, nbx] (dpg_map_localize_bounds)."""
+        e, c, g, p = self._loc_args(est, cloud, guess, params)
+        s = 1 << int(p.coarse_shift)
+        out = np.zeros((2 * int(p.half_a) + 1, (2 * int(p.half_y) + s) // s, (2 * int(p.half_x) + s) // s), np.int32)
+        check(lib().dpg_map_localize_bounds(self.handle, n_nodes, ptr(e, C.c_float), ptr(c, C.c_float), len(c),
+                                            ptr(g, C.c_float), C.byref(p), ptr(out, C.c_int32), out.size),
+              "dpg_map_localize_bounds")
+        return out
+
+    def localize_scores(self, n_nodes: int, est, cloud, guess=(0.0, 0.0, 0.0), params=None):
+        """The exact score volume of one request, int32 [2 half_a + 1, 2 half_y + 1, 2 half_x + 1]
+        (dpg_map_localize_scores)."""
+        e, c, g, p = self._loc_args(est, cloud, guess, params)
+        out = np.zeros((2 * int(p.half_a) + 1, 2 * int(p.half_y) + 1, 2 * int(p.half_x) + 1), np.int32)
+        check(lib().dpg_map_localize_scores(self.handle, n_nodes, ptr(e, C.c_float), ptr(c, C.c_float), len(c),
+                                            ptr(g, C.c_float), C.byref(p), ptr(out, C.c_int32), out.size),
+              "dpg_map_localize_scores")
         return out
 
     def beam_geometry(self, n_nodes: int, est):

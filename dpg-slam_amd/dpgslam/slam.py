@@ -117,13 +117,26 @@ class DpgSLAM:
                  non_successive_scan_constraints=True, odometry_constraints=True,
                  max_dist_within_pass=5.0, max_dist_across_passes=2.0, new_pass_std_dev=(0.2, 0.2, 0.15),
                  motion_model=(0.4, 0.4, 0.4, 0.4), display_points_fraction=10, inc_mode="isam2",
-                 loop_closure_prematch=None, prematch_min_response=0.0):
+                 loop_closure_prematch=None, prematch_min_response=0.0, new_pass_start=None,
+                 localize_min_response=0.0):
         """loop_closure_prematch: None (the reference's behaviour), or a _abi.CsmParams: reoptimize()
         then runs the correlative scan matcher (dpg_csm_batch) on its loop-closure candidates -- not
         on the successive pairs -- and starts the ICP of a candidate from the matcher's pose where
         score / (255 n_src) >= prematch_min_response, so that a candidate whose estimates drifted
         beyond ICP's correspondence distance can still close.  The per-node path (dpg_add_node, one C
-        call per node) is out of scope: it aligns from the estimates as before."""
+        call per node) is out of scope: it aligns from the estimates as before.
+
+        new_pass_start: None (the reference's behaviour: every pass starts at (0, 0, 0)), or a
+        _abi.LocParams: the first scan of every pass >= 1 is localised in the active map before its
+        node is created (dpg_map_localize over the whole map; the full circle unless the params narrow
+        it).  With status DPG_LOC_OK or DPG_LOC_UNPROVEN and score / (255 n_pts) >=
+        localize_min_response the node is created at that pose and the pass's prior carries it as its
+        mean, in reoptimize() too; otherwise the node starts at (0, 0, 0) as before.  Every attempt's
+        record is kept in last_localization."""
+        self.new_pass_start = new_pass_start
+        self.localize_min_response = float(localize_min_response)
+        self.last_localization = None                   # the record of the last new-pass localisation
+        self.pass_start_pose = {}                       # first node of a localised pass -> its prior's mean
         self.prematch_params = loop_closure_prematch
         self.prematch_min_response = float(prematch_min_response)
         self.last_prematch = None                       # the matcher's records of the last sweep
@@ -267,6 +280,23 @@ class DpgSLAM:
             p.resolution = float(resolution)
         return fn(V, self.poses, p)
 
+    def Localize(self, ranges, range_max, angle_min, angle_max, guess=None, params=None):
+        """The pose of a scan in the active map over the current node state (dpg_map_localize): a
+        LOC_RESULT_DTYPE record, pose in the map frame (the frame of GetPose).  guess None: the whole
+        map around its centre; else (x, y, theta) with the params' window around it."""
+        V = len(self.poses)
+        if V == 0:
+            raise ValueError("Localize: the graph has no node yet")
+        store = self._dpg_store()
+        fn = getattr(store, "localize", None)
+        if fn is None:
+            raise NotImplementedError(f"Localize needs a `localize(n_nodes, est, cloud, guess, params, window)` method on "
+                                      f"the backend's node store; {type(store).__name__} has none")
+        cloud = api.scan_to_cloud(np.asarray(ranges, f32), f32(angle_min), f32(angle_max), f32(range_max), self.laser)
+        if guess is None:
+            return fn(V, self.poses, cloud, (0.0, 0.0, 0.0), params, "map")
+        return fn(V, self.poses, cloud, guess, params, None)
+
     def executeDPG(self):
         """dpg_slam.cc:865-886 (dpg_execute_dpg on the node store)."""
         return self._dpg_store().execute_dpg(len(self.poses), len(self.current_pass), self.poses)
@@ -300,6 +330,8 @@ class DpgSLAM:
         keep_n = start | bool(self.odometry_constraints)
         Fn = np.zeros(V, FACTOR_DTYPE)
         Fn[start] = api.prior_factors(np.nonzero(start)[0], sigmas=self.prior_sigmas)
+        for n, pose in self.pass_start_pose.items():   # the passes that started from a localised pose
+            Fn[n] = api.prior_factor(n, pose=pose, sigmas=self.prior_sigmas)
         odo = np.nonzero(~start)[0] if self.odometry_constraints else np.zeros(0, np.int64)
         if len(odo):
             Fn[odo] = api.odometry_factors(np.asarray(self.odom_only, f32), odo - 1, odo, self.motion)
@@ -383,8 +415,14 @@ class DpgSLAM:
         """dpg_slam.cc:160-253."""
         if self.first_scan_for_pass:
             self.first_scan_for_pass = False
-            n = self._create_node(ranges, range_max, angle_min, angle_max, (0.0, 0.0, 0.0))
-            extra = api.prior_factor(n, sigmas=self.prior_sigmas)
+            start = self._new_pass_start(ranges, range_max, angle_min, angle_max)
+            if start is None:
+                n = self._create_node(ranges, range_max, angle_min, angle_max, (0.0, 0.0, 0.0))
+                extra = api.prior_factor(n, sigmas=self.prior_sigmas)
+            else:
+                n = self._create_node(ranges, range_max, angle_min, angle_max, start)
+                extra = api.prior_factor(n, pose=start, sigmas=self.prior_sigmas)
+                self.pass_start_pose[n] = start
             self.odom_only.append(self.prev_odom.copy())
             self.odom_at_last_align = self.prev_odom.copy()
             if self.pass_number == 0:   # the first node: the prior only, then optimizeGraph (:189-202)
@@ -403,6 +441,17 @@ class DpgSLAM:
         self.odom_at_last_align = self.prev_odom.copy()
         self._add_node(n, extra)
         return True
+
+    def _new_pass_start(self, ranges, range_max, angle_min, angle_max):
+        """The localised pose (x, y, theta) a pass >= 1 starts from, or None for the reference's origin."""
+        if self.new_pass_start is None or self.pass_number == 0 or not len(self.poses):
+            return None
+        r = self.Localize(ranges, range_max, angle_min, angle_max, params=self.new_pass_start)
+        self.last_localization = r
+        response = float(r["score"]) / (255.0 * max(int(r["n_pts"]), 1))
+        if int(r["status"]) not in (_abi.DPG_LOC_OK, _abi.DPG_LOC_UNPROVEN) or response < self.localize_min_response:
+            return None
+        return tuple(float(v) for v in r["pose"])
 
     def _add_node(self, n, extra, aligned=True):
         """updatePoseGraphObsConstraints (dpg_slam.cc:255-314) + optimizeGraph: the backend aligns the

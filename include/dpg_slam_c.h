@@ -919,6 +919,131 @@ float dpg_csm_kernel_ms(dpg_ctx* ctx);
 int dpg_icp_batch_prepare_guess(dpg_ctx* ctx, const int32_t* edges, int64_t n_edges, const float* guesses,
                                 const dpg_icp_params* params);
 
+/* ---- localisation of one scan in the active map: where a pass starts ----
+ * The first node of every pass is created at (0, 0, 0) (createNewPassFirstNode), so a pass has to
+ * begin where pass 0 began.  dpg_map_localize matches ONE scan against the whole active map -- the
+ * occupancy grid of the store, smoothed into a likelihood field -- over a window that may be as
+ * large as the map and the full circle, and returns the best pose.  The pair matcher above cannot do
+ * this: it needs a target node and its table lives in LDS.  The reference has no such stage.  After
+ * one float transform per point and angle all work is integer, so every output is exact and
+ * order-free, and the pruned search returns what the exhaustive one returns.
+ *
+ *   res: params.resolution, or the store's occ_grid_resolution when 0 (double).
+ *   Box (x0, y0, w, h) and occ: those of dpg_occupancy_grid(d, n_nodes, est_poses) for the same
+ *     resolution / margin_cells / max_cells (pad = 0).
+ *   lut[d2], 0 <= d2 <= R^2 (R = kernel_radius): dpg_csm_lut's bytes for ((float)res, sigma, R).
+ *   Field F, uint8 [h][w]: a cell is occupied when occ >= occupied_min (1..100, so unknown never
+ *     counts).  F[c] = the largest lut[d2] over the occupied cells of the box at squared cell
+ *     distance d2 <= R^2 from c; 0 when there is none.  Outside the box F reads 0 and is not stored.
+ *   Pooled field P, s = 1 << coarse_shift: P[x, y] = the largest F[x + i, y + j], 0 <= i, j < s, for
+ *     x in [-(s - 1), w - 1] and y in [-(s - 1), h - 1] (stored [h + s - 1][w + s - 1], index
+ *     (y + s - 1, x + s - 1)); 0 elsewhere.  P at (x, y) bounds F at every shift of an s x s block.
+ *   Rotations (dpg_loc_rotations): angle_a = (double)guess_theta + (a - half_a) (double)angle_step,
+ *     (c_a, s_a) = ((float)cos, (float)sin) of it, a = 0 .. 2 half_a.  No kernel calls a
+ *     transcendental.
+ *   Key of point (x, y) at angle a: rx = (c_a x) - (s_a y), ry = (s_a x) + (c_a y) in float, one
+ *     rounding per operation; (kx, ky) = round((double)rx / res), round((double)ry / res), C round.
+ *     A point with a non-finite coordinate or |v / res| >= 2^29 contributes nothing.
+ *   (cx, cy) = the keys of (guess_x, guess_y); an invalid key is DPG_ERR_ARG.
+ *   score(a, dx, dy), |dx| <= half_x, |dy| <= half_y: the int32 sum over the points of
+ *     F[kx + cx + dx - x0, ky + cy + dy - y0].
+ *   Blocks: nbx = ceil((2 half_x + 1) / s), nby alike.  Block (bx, by) covers dx = -half_x + bx s + i,
+ *     dy = -half_y + by s + j, i, j < s, clipped to the window.  bound(a, bx, by) = the sum over the
+ *     points of P at the block's first shift (i = j = 0), so bound >= score for every candidate of the
+ *     block, exactly.
+ *   Winner: the highest score; ties by smaller |a - half_a|, then smaller dx^2 + dy^2, then smaller a,
+ *     then smaller dy, then smaller dx (the scan matcher's order).
+ *   Pose: x = (float)((double)(cx + dx) res), y alike, theta = (float)angle_a; rot = (c_a, s_a).
+ *   Search:
+ *     1. every block's bound;
+ *     2. seeds: per angle the block with the highest bound; ties by the smaller
+ *        (2 dx0 + s - 1)^2 + (2 dy0 + s - 1)^2 ((dx0, dy0) the block's first shift: twice its centre's
+ *        distance from the window's centre), then smaller by, then smaller bx;
+ *     3. the seeds' candidates scored exactly; best0 = the best of them;
+ *     4. frontier: every block with bound >= best0 (>=, so that the tie order survives);
+ *     5. the frontier's candidates scored exactly; the winner is taken over seeds and frontier;
+ *     6. a frontier of more than max_refine_blocks blocks: the call succeeds, returns the seeds'
+ *        winner with DPG_LOC_UNPROVEN, and n_frontier reports the frontier's size.
+ *     coarse_shift = 0 is the exhaustive search (a block is a candidate).
+ *   Status: DPG_LOC_NO_OVERLAP when the returned score is 0 and either every seed's bound is 0 (then
+ *     every score is 0) or the frontier was refined; else DPG_LOC_UNPROVEN when the frontier
+ *     overflowed; else DPG_LOC_OK.  No active node (w = h = 0) succeeds with DPG_LOC_NO_OVERLAP.
+ *   Sizes: n_pts <= 2^23 (255 n_pts fits int32); (2 half_a + 1) nbx nby and (2 half_a + 1) n_pts at
+ *     most 2^29 each (DPG_ERR_SIZE beyond: the bound volume and the key table are device arrays), and
+ *     min(max_refine_blocks, blocks) s^2 at most 2^36 (one launch scores the frontier).
+ * The field is rebuilt by every call.  The call reads the store as dpg_occupancy_grid does and writes
+ * nothing of executeDPG's state or of the grid's outputs; F, P and the search buffers belong to the
+ * store, allocated at first use and regrown only for a larger request. */
+typedef struct dpg_loc_params {
+    double resolution;          /* m per cell; 0 = the store's occ_grid_resolution */
+    int64_t max_cells;          /* as dpg_grid_params */
+    int32_t margin_cells;       /* as dpg_grid_params, default 1 */
+    float sigma;                /* smoothing, m, default 0.1; finite, > 0 */
+    int32_t kernel_radius;      /* R, cells, default 3; 0 .. 7 */
+    int32_t occupied_min;       /* default 50; 1 .. 100 */
+    int32_t half_x, half_y;     /* translation window, cells, default 40, 40; 0 .. 2^15 */
+    int32_t half_a;             /* angle window, steps, default 360; 0 .. 1024 */
+    float angle_step;           /* radians per step, default 0.5 degrees; finite, > 0 */
+    int32_t coarse_shift;       /* default 4; 0 .. 5 */
+    int32_t max_refine_blocks;  /* default 16384; >= 1 */
+} dpg_loc_params;
+
+#define DPG_LOC_OK 0
+#define DPG_LOC_NO_OVERLAP 1
+#define DPG_LOC_UNPROVEN 2
+typedef struct dpg_loc_result {
+    float pose[3];              /* x, y, theta in the map frame (the frame of est_poses) */
+    float rot[2];               /* (c_a, s_a) of the winner */
+    int32_t score;              /* the winner's score */
+    int32_t score_at_guess;     /* score(half_a, 0, 0) */
+    int32_t n_pts;              /* the largest possible score is 255 n_pts */
+    int32_t best_a, best_dx, best_dy;
+    int32_t status;             /* DPG_LOC_* */
+    int32_t n_seeds;            /* 2 half_a + 1 */
+    int32_t box[4];             /* x0, y0, w, h of the field */
+    int32_t pad;
+    int64_t n_blocks;          /* (2 half_a + 1) nbx nby */
+    int64_t n_frontier;
+    int64_t n_refined_candidates;   /* in-window candidates scored in steps 3 and 5 (a seed that is
+                                       also in the frontier counts twice; an overflowed frontier: step 3 only) */
+    double ms_kernels;          /* ms_field + ms_bound + ms_fine */
+    double ms_field;            /* grid, threshold-and-stencil and pooling (HIP events) */
+    double ms_bound;            /* keys, bounds and seeds */
+    double ms_fine;             /* seed scoring, compaction, frontier scoring, reductions */
+} dpg_loc_result;
+
+#define DPG_LOC_PARAMS_SIZE 56
+#define DPG_LOC_RESULT_SIZE 128
+#ifdef __cplusplus
+ static_assert(sizeof(dpg_loc_params) == DPG_LOC_PARAMS_SIZE && sizeof(dpg_loc_result) == DPG_LOC_RESULT_SIZE, "loc ABI structs");
+#else
+ _Static_assert(sizeof(dpg_loc_params) == DPG_LOC_PARAMS_SIZE && sizeof(dpg_loc_result) == DPG_LOC_RESULT_SIZE, "loc ABI structs");
+#endif
+
+void dpg_loc_params_default(dpg_loc_params* p);
+/* Host.  DPG_OK or DPG_ERR_ARG: every field against the ranges above (resolution 0 is valid). */
+int dpg_loc_params_check(const dpg_loc_params* p);
+/* Host.  rot_out[2 half_a + 1][2] = (c_a, s_a). */
+int dpg_loc_rotations(float guess_theta, const dpg_loc_params* p, float* rot_out);
+/* The localisation of cloud_xy[n_pts][2] (body frame) around guess = (x, y, theta); blocks until
+ * *result is written (only on success).  Errors: DPG_ERR_ARG -- params, n_pts < 0 or above 2^23, an
+ * invalid guess key, NULL arguments, n_nodes out of range; DPG_ERR_STATE -- a multi-device, virtual
+ * or rank context; DPG_ERR_SIZE -- the box above max_cells, or a search above the sizes above. */
+int dpg_map_localize(dpg_dpg* d, int64_t n_nodes, const float* est_poses, const float* cloud_xy, int64_t n_pts,
+                     const float guess[3], const dpg_loc_params* params, dpg_loc_result* result);
+/* Diagnostics.  Each: cap in elements of out, DPG_ERR_SIZE with nothing written when too small.
+ * dpg_map_field: shift < 0 -- F [h][w]; shift 0 .. 5 -- P at that shift (params' coarse_shift is not
+ * read), [h + s - 1][w + s - 1]; box receives x0, y0, w, h (also when out is NULL: plan only). */
+int dpg_map_field(dpg_dpg* d, int64_t n_nodes, const float* est_poses, const dpg_loc_params* params, int32_t shift,
+                  uint8_t* out, int64_t cap, int32_t box[4]);
+/* the bound volume, out[2 half_a + 1][nby][nbx] */
+int dpg_map_localize_bounds(dpg_dpg* d, int64_t n_nodes, const float* est_poses, const float* cloud_xy, int64_t n_pts,
+                            const float guess[3], const dpg_loc_params* params, int32_t* out, int64_t cap);
+/* the exact score volume, out[2 half_a + 1][2 half_y + 1][2 half_x + 1], from the search's own fine
+ * kernel run over every block */
+int dpg_map_localize_scores(dpg_dpg* d, int64_t n_nodes, const float* est_poses, const float* cloud_xy, int64_t n_pts,
+                            const float guess[3], const dpg_loc_params* params, int32_t* out, int64_t cap);
+
 #ifdef __cplusplus
 }
 #endif
