@@ -4,6 +4,10 @@
 // store, batched and single ICP, covariance), dpg_gn_api.hip (pose graph, marginals) and
 // dpg_sweep.hip (re-linearisation sweep, dpg_add_node); the few functions they call across each
 // other are declared at the end.  Nothing here is exported from the library.
+// Every device array, pinned or host-mapped block, event, stream and solver handle of the layer is a
+// member that releases itself (DevBuf / PinBuf / MappedBuf, DevEvent, DevStream, CholPtr) of the
+// context, its batch graph (GnGraph), its collective thread (HostColl) or a child: the release calls
+// are in this header only.  Kernels and launchers take raw pointers; dpg_gn_dev is such a view.
 #ifndef DPG_CTX_H
 #define DPG_CTX_H
 
@@ -55,8 +59,9 @@ T or_default(const T* p, void (*def)(T*)) {
     return v;
 }
 
-// The two memory kinds of OwnedBuf (dpg_buf.h): device memory, whose copy is stream-ordered and
-// waited for, and default-flags pinned host memory.
+// The three memory kinds of OwnedBuf (dpg_buf.h): device memory, whose copy is stream-ordered and
+// waited for; default-flags pinned host memory; and host-mapped coherent (fine-grained) host memory
+// for the few words that a kernel and the host poll across the bus while both run.
 struct DevMem {
     typedef hipStream_t stream_t;
     static int alloc(void** p, size_t bytes) { return hipMalloc(p, bytes) != hipSuccess; }
@@ -75,10 +80,15 @@ struct PinMem {
         return 0;
     }
 };
+struct MappedMem : PinMem {
+    static int alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess; }
+};
 template <typename T>
 using DevBuf = OwnedBuf<T, DevMem>;
 template <typename T>
 using PinBuf = OwnedBuf<T, PinMem>;
+template <typename T>
+using MappedBuf = OwnedBuf<T, MappedMem>;
 
 // An event (a stream) that owns itself: created on first use, destroyed with its owner.  Move-only.
 struct DevEvent {
@@ -101,26 +111,52 @@ struct DevStream {
     DevStream() = default;
     DevStream(const DevStream&) = delete;
     DevStream& operator=(const DevStream&) = delete;
-    ~DevStream() {
+    ~DevStream() { release(); }
+    void release() {
         if (s) (void)hipStreamDestroy(s);
+        s = nullptr;
     }
 };
+// the supernodal Cholesky's handle (dpg_chol.hip), destroyed with its owner
+struct CholDestroy { void operator()(void* h) const { dpg_chol_destroy(h); } };
+typedef std::unique_ptr<void, CholDestroy> CholPtr;
 
+// The batch pose graph (dpg_gn.hip): its arrays, pinned scalars and solver, and `v`, the view of them
+// that every launcher takes.  Move-assignment swaps: the moved-from object releases the previous graph.
+struct GnGraph {
+    dpg_gn_dev v{};
+    DevBuf<dpg_factor> factors;
+    DevBuf<int32_t> up_cptr, up_clist, rowptr, colidx, src_up;
+    DevBuf<double> bsr, minv, poses, x, r, z, p0, p1, q, partials, scal, hb_own, scal3;
+    PinBuf<double> scal3_host;
+    DevBuf<uint8_t> mine;        // multi-device forms (dpg_gn_dev_set_ownership)
+    DevBuf<double> hb_part;
+    CholPtr chol;                // empty if the analysis failed (the PCG solver still works)
+    // into an empty owner, which a failure leaves empty: host work first (pattern, lists, the Cholesky's analysis
+    // and plan), then -- after hipStreamSynchronize(sync_stream) when given -- the device allocations and uploads
+    int build(int64_t n_nodes, const dpg_factor* factors, int64_t n_factors, int64_t shard_begin, int64_t shard_end,
+              const dpg_chol_opts* opts, hipStream_t sync_stream);
+};
+
+// Members are destroyed in reverse order of declaration, so the streams go last, after the events
+// recorded on them and the buffers their work used.  Nothing is in flight by then:
+// dpg_ctx_destroy drains the stream (after joining the covariance on `aux`) and stops the
+// collective thread before `delete`, which is what makes every order of release safe.
 struct dpg_ctx {
     int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    hipEvent_t ev[8] = {};
+    DevStream own;                  // the stream made at creation, until the caller sets another
+    hipStream_t stream = nullptr;   // the stream in use: own.s or the caller's
     // the batch covariance runs on `aux` beside what follows the ICP on `stream` (the pose graph
     // does not read it): ev[2] marks its end, cov_pending until `stream` has been made to wait
-    hipStream_t aux = nullptr;
+    DevStream aux;
+    DevEvent ev[8];
     bool cov_pending = false, cov_on_aux = false;
     int32_t icp_variant = DPG_ICP_ANGULAR;
     int32_t defer_cap = 256;        // angular ICP: cooperative-queue threshold (dpg_ctx_set_icp_defer_cap)
     int32_t cov_wg = 256;           // covariance kernel workgroups beside the pose graph (dpg_ctx_set_cov_workgroups)
     int32_t kernel_variant = 0;     // angular ICP kernel form (dpg_ctx_set_icp_kernel_variant, A/B)
     float map_ms = 0.f;             // last dpg_get_map kernel (HIP events map_ev)
-    hipEvent_t map_ev[2] = {};
+    DevEvent map_ev[2];             // created by the first dpg_get_map
     // scan store (batch form)
     DevBuf<float> full, ds;
     DevBuf<int64_t> ds_off_dev;
@@ -155,7 +191,7 @@ struct dpg_ctx {
     DevBuf<uint16_t> s_tree_idx;
     DevBuf<uint16_t> s_buckets;
     // pose graph
-    dpg_gn_dev gn{};
+    GnGraph gn;
     bool gn_ready = false;
     dpg_gn_params gp{};
     float asm_ms = 0.f, solve_ms = 0.f;
@@ -163,9 +199,9 @@ struct dpg_ctx {
     // device's factor list by the first dpg_gn_marginal_pairs after a setup
     std::vector<uint64_t> gn_pairs;
     bool gn_pairs_valid = false;
-    // the pipelined GN loop (dpg_gn_pipe.h): control block, two host-mapped report slots + events
-    dpg_gn_ctl* pipe_ctl = nullptr;
-    dpg_gn_slot* pipe_slot = nullptr;
+    // the first pipelined GN loop's (dpg_gn_pipe.h): control block; host-mapped report slots [2] + the initial error's
+    DevBuf<dpg_gn_ctl> pipe_ctl;
+    MappedBuf<dpg_gn_slot> pipe_slot;
     uint32_t pipe_loop = 0;            // loops run on this device (tags their reports)
     // multi-device forms (dpg_ctx_create_multi / _rank / _virtual): this context drives local
     // device 0 and holds the batch as the caller sees it; `peers` are full single-device contexts
@@ -217,14 +253,13 @@ struct dpg_ctx {
 // place and stores the tag.  Stream order serializes the buffer's uses (the next copy into it
 // follows this iteration's copy out of it).  A failed collective still stores the tag (the stream
 // moves on) and sets `failed`, which the loop checks at every report.
-// Owns its thread, pinned buffers and events (dpg_gn_api.hip): create() hands out a complete
-// object or an error; the destructor stops and joins the thread (its queue is empty once the
-// context's stream has drained), then frees, with the context's device current.
+// Owns its thread, buffers and events (dpg_gn_api.hip): create() hands out a complete object or an
+// error; the destructor stops and joins the thread (its queue is empty once the context's stream
+// has drained); the members then release themselves, with the context's device current.
 struct dpg_ctx::HostColl {
     PinBuf<double> buf;              // pinned: the packed system, summed in place
-    uint32_t* flag = nullptr;        // host-mapped: the last tag the thread completed
-    uint32_t* timed_out = nullptr;   // host-mapped: the wait kernel gave up (no tag in 120 s)
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    MappedBuf<uint32_t> flag;        // host-mapped: [0] the last tag the thread completed, [1] the wait kernel gave up (120 s)
+    DevEvent ev[2];
     uint32_t next_tag = 0;
     std::thread th;
     std::mutex mu;
@@ -253,7 +288,7 @@ inline bool is_multi(const dpg_ctx* c) { return c->coll != kCollNone; }
 inline int join_cov(dpg_ctx* c) {
     if (!c->cov_pending) return DPG_OK;
     c->cov_pending = false;
-    return hipStreamWaitEvent(c->stream, c->ev[2], 0) == hipSuccess ? DPG_OK : DPG_ERR_HIP;
+    return hipStreamWaitEvent(c->stream, c->ev[2].e, 0) == hipSuccess ? DPG_OK : DPG_ERR_HIP;
 }
 
 // Localisation in the active map (dpg_loc.hip): the field, its pooled form and the search buffers.

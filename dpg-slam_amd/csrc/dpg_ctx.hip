@@ -98,15 +98,15 @@ dpg_ctx* dpg_ctx_create(int device) {
     if (hipSetDevice(device) != hipSuccess) return no_ctx(fail(DPG_ERR_HIP, "hipSetDevice(%d) failed", device));
     dpg_ctx* c = new dpg_ctx();
     c->device = device;
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
+    if (hipStreamCreateWithFlags(&c->own.s, hipStreamNonBlocking) != hipSuccess) {
         delete c;
         return no_ctx(fail(DPG_ERR_HIP, "hipStreamCreate failed"));
     }
-    c->own_stream = true;
+    c->stream = c->own.s;
     // the side stream of the timed batch's covariance (beside the pose graph) is the context's too:
     // created with it, not inside the first solve (a stream creation costs ~7 ms on this stack)
-    if (hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking) != hipSuccess) c->aux = nullptr;
-    for (auto& e : c->ev) (void)hipEventCreate(&e);
+    if (hipStreamCreateWithFlags(&c->aux.s, hipStreamNonBlocking) != hipSuccess) c->aux.s = nullptr;
+    for (auto& e : c->ev) (void)e.ensure(hipEventDefault);
     dpg_gn_params_default(&c->gp);
     return c;
 }
@@ -161,9 +161,8 @@ dpg_ctx* dpg_ctx_create_virtual(int32_t k, int32_t device) {
             dpg_ctx_destroy(c);
             return nullptr;
         }
-        (void)hipStreamDestroy(q->stream);
+        q->own.release();
         q->stream = c->stream;
-        q->own_stream = false;
         q->rank = r;
         c->peers.push_back(q);
     }
@@ -324,8 +323,8 @@ void dpg_ctx_release_child(dpg_ctx* c, void* child) {
         }
 }
 
-// Order: children, peers, communicators, drain the stream, the collective thread, then the rest.
-// The device arrays free themselves with the context (delete), this device current.
+// Order: children, peers, communicators, drain the stream, the collective thread, then the rest: graph, arrays,
+// events and streams are members and go with the context (delete), this device current, nothing in flight.
 void dpg_ctx_destroy(dpg_ctx* c) {
     if (!c) return;
     while (!c->children.empty()) {   // each child's destroy releases itself from the list
@@ -343,13 +342,6 @@ void dpg_ctx_destroy(dpg_ctx* c) {
     (void)join_cov(c);
     (void)hipStreamSynchronize(c->stream);
     c->hc.reset();
-    if (c->aux) (void)hipStreamDestroy(c->aux);
-    if (c->gn_ready) dpg_gn_dev_free(&c->gn);
-    if (c->pipe_ctl) (void)hipFree(c->pipe_ctl);
-    if (c->pipe_slot) (void)hipHostFree(c->pipe_slot);
-    for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
-    for (auto& e : c->map_ev) if (e) (void)hipEventDestroy(e);
-    if (c->own_stream) (void)hipStreamDestroy(c->stream);
     if (c == g_default_ctx) g_default_ctx = nullptr;
     delete c;
 }
@@ -358,9 +350,8 @@ int dpg_ctx_set_stream(dpg_ctx* c, void* s) {
     if (!c) return fail(DPG_ERR_ARG, "ctx is NULL");
     if (join_cov(c)) return fail(DPG_ERR_HIP, "stream wait failed");
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->own_stream) (void)hipStreamDestroy(c->stream);
+    c->own.release();
     c->stream = reinterpret_cast<hipStream_t>(s);
-    c->own_stream = false;
     if (c->coll == kCollVirtual)   // the virtual devices keep sharing one stream
         for (dpg_ctx* q : c->peers) q->stream = c->stream;
     return DPG_OK;

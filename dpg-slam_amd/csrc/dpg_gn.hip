@@ -415,14 +415,9 @@ __global__ void scalars_kernel(const double* __restrict__ chi2, const int32_t* _
     scal3[2] = status ? (double)*status : 0.0;
 }
 
-// ICP results -> BetweenFactor measurement + diagonal information (dpg_slam.cc:331-338)
-__global__ void icp_to_factor_kernel(const dpg_icp_result* __restrict__ res, dpg_factor* __restrict__ F,
-                                     int64_t first, int64_t count, int64_t n_always, double ix, double iy,
-                                     double ith) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= count) return;
-    dpg_factor& f = F[first + e];
-    const dpg_icp_result r = res[e];
+// ICP result r of batch slot e -> BetweenFactor measurement + diagonal information (dpg_slam.cc:331-338)
+__device__ __forceinline__ void icp_factor_write(dpg_factor& f, const dpg_icp_result& r, int64_t e, int64_t n_always,
+                                                 double ix, double iy, double ith) {
     const bool keep = e < n_always || (r.converged && r.status == DPG_ICP_OK);
     f.z[0] = r.z[0];
     f.z[1] = r.z[1];
@@ -432,10 +427,22 @@ __global__ void icp_to_factor_kernel(const dpg_icp_result* __restrict__ res, dpg
     f.info[2] = keep ? ith : 0.0;
 }
 
-template <typename T>
-int dev_alloc(T** p, size_t n) {
-    if (n == 0) n = 1;
-    return hipMalloc(reinterpret_cast<void**>(p), n * sizeof(T)) == hipSuccess ? 0 : DPG_ERR_HIP;
+__global__ void icp_to_factor_kernel(const dpg_icp_result* __restrict__ res, dpg_factor* __restrict__ F,
+                                     int64_t first, int64_t count, int64_t n_always, double ix, double iy,
+                                     double ith) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= count) return;
+    dpg_factor& f = F[first + e];
+    const dpg_icp_result r = res[e];
+    icp_factor_write(f, r, e, n_always, ix, iy, ith);
+}
+
+// an empty buffer sized and the view's pointer set to it
+template <typename B, typename T>
+int take(B& b, T*& view, size_t n) {
+    const int rc = b.reserve(n);
+    view = b.p;
+    return rc;
 }
 
 template <typename T>
@@ -452,20 +459,9 @@ inline unsigned nblk(int64_t n) { return (unsigned)((n + kRowThreads - 1) / kRow
 extern "C" int64_t dpg_gn_dev_vote_offset(const dpg_gn_dev* g) { return 9 * g->nnzb_upper + 3 * g->n_nodes + 2; }
 extern "C" int64_t dpg_gn_dev_hb_size(const dpg_gn_dev* g) { return dpg_gn_dev_vote_offset(g) + g->n_vote; }
 
-extern "C" void dpg_gn_dev_free(dpg_gn_dev* g) {
-    void* ptrs[] = {g->factors, g->up_row, g->up_col, g->up_cptr, g->up_clist, g->node_fptr, g->node_flist,
-                    g->rowptr, g->colidx, g->src_up, g->bsr, g->minv, g->poses, g->x, g->r, g->z,
-                    g->p0, g->p1, g->q, g->partials, g->scal, g->hb_own, g->scal3, g->mine, g->hb_part};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    if (g->scal3_host) (void)hipHostFree(g->scal3_host);
-    if (g->chol) dpg_chol_destroy(g->chol);
-    memset(g, 0, sizeof(*g));
-}
-
-extern "C" int dpg_gn_dev_alloc(dpg_gn_dev* g, int64_t n, const dpg_factor* F, int64_t nf,
-                                int64_t shard_begin, int64_t shard_end, const dpg_chol_opts* opts, void* sync_stream) {
-    memset(g, 0, sizeof(*g));
+int GnGraph::build(int64_t n, const dpg_factor* F, int64_t nf, int64_t shard_begin, int64_t shard_end,
+                   const dpg_chol_opts* opts, hipStream_t sync_stream) {
+    dpg_gn_dev* g = &v;
     if (n <= 0 || nf < 0 || n > (int64_t)1 << 28) return DPG_ERR_ARG;
     const double t0 = now_ms();
     // unique pairs (lo, hi) of Between factors, as sorted 64-bit keys lo << 32 | hi; every
@@ -484,6 +480,7 @@ extern "C" int dpg_gn_dev_alloc(dpg_gn_dev* g, int64_t n, const dpg_factor* F, i
         fkey[(size_t)k] = (uint64_t)std::min(f.i, f.j) << 32 | (uint64_t)std::max(f.i, f.j);
         pk.push_back(fkey[(size_t)k]);
     }
+    const size_t n_between = pk.size();
     std::sort(pk.begin(), pk.end());
     pk.erase(std::unique(pk.begin(), pk.end()), pk.end());
     const int64_t P = (int64_t)pk.size();
@@ -511,27 +508,9 @@ extern "C" int dpg_gn_dev_alloc(dpg_gn_dev* g, int64_t n, const dpg_factor* F, i
     for (int64_t k = 0; k < nf; ++k)
         if (fkey[(size_t)k] != ~0ull)
             fpair[(size_t)k] = (int32_t)(std::lower_bound(pk.begin(), pk.end(), fkey[(size_t)k]) - pk.begin());
-    // contribution lists per upper block (factor order)
-    std::vector<int32_t> cnt((size_t)nu + 1, 0);
-    for (int64_t k = 0; k < nf; ++k) {
-        const dpg_factor& f = F[k];
-        cnt[(size_t)f.i + 1]++;
-        if (f.kind == DPG_FACTOR_BETWEEN) {
-            cnt[(size_t)f.j + 1]++;
-            cnt[(size_t)(n + fpair[(size_t)k]) + 1]++;
-        }
-    }
-    for (int64_t u = 0; u < nu; ++u) cnt[(size_t)u + 1] += cnt[(size_t)u];
-    std::vector<int32_t> cptr = cnt, clist((size_t)cnt[(size_t)nu]);
-    std::vector<int32_t> cur(cnt.begin(), cnt.end() - 1);
-    for (int64_t k = 0; k < nf; ++k) {
-        const dpg_factor& f = F[k];
-        clist[(size_t)cur[(size_t)f.i]++] = (int32_t)(k << 2 | 0);
-        if (f.kind == DPG_FACTOR_BETWEEN) {
-            clist[(size_t)cur[(size_t)f.j]++] = (int32_t)(k << 2 | 1);
-            clist[(size_t)cur[(size_t)(n + fpair[(size_t)k])]++] = (int32_t)(k << 2 | (f.i < f.j ? 2 : 3));
-        }
-    }
+    // contribution lists per upper block: one entry per prior, three per Between
+    std::vector<int32_t> cptr((size_t)nu + 1), clist((size_t)nf + 2 * n_between);
+    dpg_contribution_lists(F, nf, n, fpair.data(), P, cptr.data(), clist.data());
     // full BSR rows, by column: row v is the pairs (u, v) with u < v in ascending u (the key order
     // deals them so, bucketed by v), the diagonal block, then the pairs (v, w) in ascending w
     std::vector<int32_t> rowptr((size_t)n + 1, 0);
@@ -557,12 +536,9 @@ extern "C" int dpg_gn_dev_alloc(dpg_gn_dev* g, int64_t n, const dpg_factor* F, i
         }
     }
     const double t1 = now_ms();
-    void* chol = sym_job.get();
+    CholPtr ch(sym_job.get());
     const double t2 = now_ms();
-    if (sync_stream && hipStreamSynchronize(reinterpret_cast<hipStream_t>(sync_stream)) != hipSuccess) {
-        if (chol) dpg_chol_destroy(chol);
-        return DPG_ERR_HIP;
-    }
+    if (sync_stream && hipStreamSynchronize(sync_stream) != hipSuccess) return DPG_ERR_HIP;
     g->n_nodes = n;
     g->n_factors = nf;
     g->nnzb_upper = nu;
@@ -571,37 +547,36 @@ extern "C" int dpg_gn_dev_alloc(dpg_gn_dev* g, int64_t n, const dpg_factor* F, i
     g->shard_end = shard_end > nf ? nf : shard_end;
     g->n_blocks_rows = (int32_t)nblk(n);
     int rc = 0;
-    rc |= dev_alloc(&g->factors, (size_t)nf);
-    rc |= dev_alloc(&g->up_cptr, cptr.size());
-    rc |= dev_alloc(&g->up_clist, clist.size());
-    rc |= dev_alloc(&g->rowptr, rowptr.size());
-    rc |= dev_alloc(&g->colidx, colidx.size());
-    rc |= dev_alloc(&g->src_up, srcup.size());
-    rc |= dev_alloc(&g->bsr, 9 * colidx.size());
-    rc |= dev_alloc(&g->minv, 9 * (size_t)n);
-    rc |= dev_alloc(&g->poses, 3 * (size_t)n);
-    rc |= dev_alloc(&g->x, 3 * (size_t)n);
-    rc |= dev_alloc(&g->r, 3 * (size_t)n);
-    rc |= dev_alloc(&g->z, 3 * (size_t)n);
-    rc |= dev_alloc(&g->p0, 3 * (size_t)n);
-    rc |= dev_alloc(&g->p1, 3 * (size_t)n);
-    rc |= dev_alloc(&g->q, 3 * (size_t)n);
-    rc |= dev_alloc(&g->partials, 6 * (size_t)g->n_blocks_rows + (size_t)n);
-    rc |= dev_alloc(&g->scal, 2 * (size_t)65536);
-    rc |= dev_alloc(&g->hb_own, (size_t)dpg_gn_dev_hb_size(g));
-    rc |= dev_alloc(&g->scal3, 4);
-    if (!rc && hipHostMalloc(reinterpret_cast<void**>(&g->scal3_host), 4 * sizeof(double)) != hipSuccess) rc = DPG_ERR_HIP;
-    if (rc) { if (chol) dpg_chol_destroy(chol); dpg_gn_dev_free(g); return DPG_ERR_HIP; }
-    if (nf && hipMemcpy(g->factors, F, (size_t)nf * sizeof(dpg_factor), hipMemcpyHostToDevice) != hipSuccess) rc = DPG_ERR_HIP;
-    rc |= up(g->up_cptr, cptr);
-    rc |= up(g->up_clist, clist);
-    rc |= up(g->rowptr, rowptr);
-    rc |= up(g->colidx, colidx);
-    rc |= up(g->src_up, srcup);
-    if (rc) { if (chol) dpg_chol_destroy(chol); dpg_gn_dev_free(g); return DPG_ERR_HIP; }
+    // (a graph without factors still hands the kernels one element)
+    rc |= take(factors, g->factors, std::max<size_t>((size_t)nf, 1));
+    rc |= take(up_cptr, g->up_cptr, cptr.size());
+    rc |= take(up_clist, g->up_clist, std::max<size_t>(clist.size(), 1));
+    rc |= take(this->rowptr, g->rowptr, rowptr.size());   // (the members behind the host vectors of the same names)
+    rc |= take(this->colidx, g->colidx, colidx.size());
+    rc |= take(src_up, g->src_up, srcup.size());
+    rc |= take(bsr, g->bsr, 9 * colidx.size());
+    rc |= take(minv, g->minv, 9 * (size_t)n);
+    rc |= take(poses, g->poses, 3 * (size_t)n);
+    rc |= take(x, g->x, 3 * (size_t)n);
+    rc |= take(r, g->r, 3 * (size_t)n);
+    rc |= take(z, g->z, 3 * (size_t)n);
+    rc |= take(p0, g->p0, 3 * (size_t)n);
+    rc |= take(p1, g->p1, 3 * (size_t)n);
+    rc |= take(q, g->q, 3 * (size_t)n);
+    rc |= take(partials, g->partials, 6 * (size_t)g->n_blocks_rows + (size_t)n);
+    rc |= take(scal, g->scal, 2 * (size_t)65536);
+    rc |= take(hb_own, g->hb_own, (size_t)dpg_gn_dev_hb_size(g));
+    rc |= take(scal3, g->scal3, 4);
+    rc |= take(scal3_host, g->scal3_host, 4);
+    if (!rc && nf && hipMemcpy(g->factors, F, (size_t)nf * sizeof(dpg_factor), hipMemcpyHostToDevice) != hipSuccess) rc = -1;
+    if (!rc)
+        rc = up(g->up_cptr, cptr) | up(g->up_clist, clist) | up(g->rowptr, rowptr) | up(g->colidx, colidx) |
+             up(g->src_up, srcup);
+    if (rc) { *this = GnGraph(); return DPG_ERR_HIP; }
     // the supernodal Cholesky's device structures (once per pattern)
-    g->chol = chol;
+    g->chol = ch.release();
     if (g->chol && dpg_chol_create_sym_upload(&g->chol)) g->chol = nullptr;   // (destroyed on error)
+    chol.reset(g->chol);   // the view's handle is the owner's
     if (g->chol) dpg_chol_keep_inverse(g->chol, 1);   // chord steps reuse the factor: L11^-1 for their solves
     const double t3 = now_ms();
     double bt[2] = {0.0, 0.0};
@@ -649,7 +624,7 @@ __global__ void own_kernel(uint8_t* __restrict__ mine, int64_t nf, int32_t world
     if (f < nf) mine[f] = (f % world) == rank ? 1 : 0;
 }
 
-// icp_to_factor_kernel's expressions for this device's results, written to the caller's slots
+// this device's results, written to the caller's slots
 __global__ void icp_to_factor_scatter_kernel(const dpg_icp_result* __restrict__ res, const int32_t* __restrict__ idx,
                                              dpg_factor* __restrict__ F, uint8_t* __restrict__ mine, int64_t first,
                                              int64_t n_local, int64_t n_always, double ix, double iy, double ith) {
@@ -658,13 +633,7 @@ __global__ void icp_to_factor_scatter_kernel(const dpg_icp_result* __restrict__ 
     const int64_t e = idx[j];
     dpg_factor& f = F[first + e];
     const dpg_icp_result r = res[j];
-    const bool keep = e < n_always || (r.converged && r.status == DPG_ICP_OK);
-    f.z[0] = r.z[0];
-    f.z[1] = r.z[1];
-    f.z[2] = r.z[2];
-    f.info[0] = keep ? ix : 0.0;
-    f.info[1] = keep ? iy : 0.0;
-    f.info[2] = keep ? ith : 0.0;
+    icp_factor_write(f, r, e, n_always, ix, iy, ith);
     mine[first + e] = 1;
 }
 
@@ -681,20 +650,21 @@ __global__ void vsum_kernel(VsumArgs a, int32_t k, int64_t n) {
     }
 }
 
-extern "C" int dpg_gn_dev_set_ownership(dpg_gn_dev* g, int32_t world, int32_t rank, void* stream) {
+extern "C" int dpg_gn_dev_set_ownership(GnGraph* o, int32_t world, int32_t rank, void* stream) {
     if (world < 1 || rank < 0 || rank >= world) return DPG_ERR_ARG;
+    dpg_gn_dev* g = &o->v;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int32_t nv = world > 1 ? 2 * world : 0;
-    if (nv != g->n_vote) {   // the packed buffers grow by the vote words
+    if (nv != g->n_vote) {   // the packed buffers grow by the vote words, once the stream is done with them
         if (hipStreamSynchronize(s) != hipSuccess) return DPG_ERR_HIP;
-        if (g->hb_own) (void)hipFree(g->hb_own);
-        if (g->hb_part) (void)hipFree(g->hb_part);
-        g->hb_own = g->hb_part = nullptr;
+        o->hb_own.release();
+        o->hb_part.release();
+        g->hb_part = nullptr;
         g->n_vote = nv;
-        if (dev_alloc(&g->hb_own, (size_t)dpg_gn_dev_hb_size(g))) return DPG_ERR_HIP;
+        if (take(o->hb_own, g->hb_own, (size_t)dpg_gn_dev_hb_size(g))) return DPG_ERR_HIP;
     }
-    if (!g->mine && dev_alloc(&g->mine, (size_t)g->n_factors)) return DPG_ERR_HIP;
-    if (!g->hb_part && dev_alloc(&g->hb_part, (size_t)dpg_gn_dev_hb_size(g))) return DPG_ERR_HIP;
+    if (!o->mine.p && take(o->mine, g->mine, std::max<size_t>((size_t)g->n_factors, 1))) return DPG_ERR_HIP;
+    if (!o->hb_part.p && take(o->hb_part, g->hb_part, (size_t)dpg_gn_dev_hb_size(g))) return DPG_ERR_HIP;
     // the other devices' vote words stay zero in this device's partial buffer
     if (hipMemsetAsync(g->hb_part, 0, sizeof(double) * (size_t)dpg_gn_dev_hb_size(g), s) != hipSuccess) return DPG_ERR_HIP;
     g->world = world;

@@ -17,12 +17,12 @@ static int gn_setup_1(dpg_ctx* c, int64_t V, const dpg_factor* F, int64_t nf, in
                       const dpg_gn_params* gp) {
     HIP_TRY(hipSetDevice(c->device));
     // the new graph's host work overlaps what still runs on the stream (a batch's ICP); the
-    // stream is drained before the device allocations, and the previous graph freed after them
-    dpg_gn_dev ng;
-    int rc = dpg_gn_dev_alloc(&ng, V, F, nf, b, e, &c->copts, c->stream);
+    // stream is drained before the device allocations, and the previous graph released after them
+    // (it goes to `ng` in the move and away with it); a failed build leaves the previous graph live
+    GnGraph ng;
+    int rc = ng.build(V, F, nf, b, e, &c->copts, c->stream);
     if (rc) return fail(rc, "pose-graph setup failed (invalid factor or out of memory)");
-    if (c->gn_ready) dpg_gn_dev_free(&c->gn);
-    c->gn = ng;
+    c->gn = std::move(ng);
     c->gn_ready = true;
     c->gn_pairs_valid = false;
     c->gp = or_default(gp, dpg_gn_params_default);
@@ -32,14 +32,14 @@ static int gn_setup_1(dpg_ctx* c, int64_t V, const dpg_factor* F, int64_t nf, in
 static int gn_set_poses_1(dpg_ctx* c, const double* poses) {
     if (!c->gn_ready) return fail(DPG_ERR_STATE, "graph not set up");
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpyAsync(c->gn.poses, poses, sizeof(double) * 3 * (size_t)c->gn.n_nodes, hipMemcpyHostToDevice,
+    HIP_TRY(hipMemcpyAsync(c->gn.v.poses, poses, sizeof(double) * 3 * (size_t)c->gn.v.n_nodes, hipMemcpyHostToDevice,
                            c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->gn.have_factor = 0;            // a new linearization point: the next solve refactors
-    c->gn.last_delta_inf = 1e300;
-    c->gn.prev_delta_inf = 1e300;
-    c->gn.last_was_chord = 0;
-    c->gn.n_factorizations = 0;
+    c->gn.v.have_factor = 0;            // a new linearization point: the next solve refactors
+    c->gn.v.last_delta_inf = 1e300;
+    c->gn.v.prev_delta_inf = 1e300;
+    c->gn.v.last_was_chord = 0;
+    c->gn.v.n_factorizations = 0;
     return DPG_OK;
 }
 
@@ -53,26 +53,26 @@ static int gn_set_poses_1(dpg_ctx* c, const double* poses) {
 
 // enqueue solve + retract on one device (no multi check: the multi-device host loop uses it per device)
 static int solve_retract_async_1(dpg_ctx* c, const double* hb_dev) {
-    if (!hb_dev) hb_dev = c->gn.hb_own;
-    HIP_TRY(hipEventRecord(c->ev[4], c->stream));
-    int rc = dpg_gn_dev_solve_async(&c->gn, hb_dev, &c->gp, c->stream);
+    if (!hb_dev) hb_dev = c->gn.v.hb_own;
+    HIP_TRY(hipEventRecord(c->ev[4].e, c->stream));
+    int rc = dpg_gn_dev_solve_async(&c->gn.v, hb_dev, &c->gp, c->stream);
     if (rc) return fail(rc, "solve launch failed: %s", hipGetErrorString(hipGetLastError()));
-    HIP_TRY(hipEventRecord(c->ev[5], c->stream));
+    HIP_TRY(hipEventRecord(c->ev[5].e, c->stream));
     return DPG_OK;
 }
 
 static int fetch_1(dpg_ctx* c, const double* hb_dev, double out[3]) {
-    if (!hb_dev) hb_dev = c->gn.hb_own;
-    int rc = dpg_gn_dev_fetch(&c->gn, hb_dev, c->stream, out);
+    if (!hb_dev) hb_dev = c->gn.v.hb_own;
+    int rc = dpg_gn_dev_fetch(&c->gn.v, hb_dev, c->stream, out);
     if (rc) return fail(rc, "fetch failed");
     float s = 0.f;
-    if (hipEventElapsedTime(&s, c->ev[4], c->ev[5]) == hipSuccess) c->solve_ms = s;
+    if (hipEventElapsedTime(&s, c->ev[4].e, c->ev[5].e) == hipSuccess) c->solve_ms = s;
     return DPG_OK;
 }
 
 static int read_error(dpg_ctx* c, double* err) {
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpyAsync(err, c->gn.hb_own + 9 * c->gn.nnzb_upper + 3 * c->gn.n_nodes, sizeof(double),
+    HIP_TRY(hipMemcpyAsync(err, c->gn.v.hb_own + 9 * c->gn.v.nnzb_upper + 3 * c->gn.v.n_nodes, sizeof(double),
                            hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return DPG_OK;
@@ -90,13 +90,13 @@ static int check_conv(const dpg_gn_params* gp, double cur, double nw) {
 // the virtual devices' rank-order sum.  Out of place, so an iteration that a gate turned into
 // no-ops sums the same partial buffers again and leaves hb_own as it was.
 static int coll_sum_hb(dpg_ctx* c) {
-    const size_t count = (size_t)dpg_gn_dev_hb_size(&c->gn);
+    const size_t count = (size_t)dpg_gn_dev_hb_size(&c->gn.v);
     if (c->coll == kCollVirtual) {
         const double* parts[kMaxVirtual];
         double* outs[kMaxVirtual];
         for (int k = 0; k < n_dev(c); ++k) {
-            parts[k] = dev_ctx(c, k)->gn.hb_part;
-            outs[k] = dev_ctx(c, k)->gn.hb_own;
+            parts[k] = dev_ctx(c, k)->gn.v.hb_part;
+            outs[k] = dev_ctx(c, k)->gn.v.hb_own;
         }
         const int rc = dpg_launch_vsum(parts, outs, n_dev(c), (int64_t)count, c->stream);   // the shared stream
         return rc ? fail(rc, "virtual all-reduce launch failed") : DPG_OK;
@@ -104,18 +104,18 @@ static int coll_sum_hb(dpg_ctx* c) {
     if (c->coll == kCollHost) {   // the caller's collective, through host memory (blocking)
         c->host_hb.resize(count);
         HIP_TRY(hipSetDevice(c->device));
-        HIP_TRY(hipMemcpyAsync(c->host_hb.data(), c->gn.hb_part, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->host_hb.data(), c->gn.v.hb_part, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         if (c->host_ops.allreduce_sum_f64(c->host_ops.user, c->host_hb.data(), (int64_t)count))
             return fail(DPG_ERR_HIP, "the caller's all-reduce of the packed system failed");
-        HIP_TRY(hipMemcpyAsync(c->gn.hb_own, c->host_hb.data(), sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->gn.v.hb_own, c->host_hb.data(), sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         return DPG_OK;
     }
     if (ncclGroupStart() != ncclSuccess) return fail(DPG_ERR_HIP, "ncclGroupStart failed");
     for (int k = 0; k < n_dev(c); ++k) {
         dpg_ctx* q = dev_ctx(c, k);
-        const ncclResult_t r = ncclAllReduce(q->gn.hb_part, q->gn.hb_own, count, ncclDouble, ncclSum, c->comms[(size_t)k],
+        const ncclResult_t r = ncclAllReduce(q->gn.v.hb_part, q->gn.v.hb_own, count, ncclDouble, ncclSum, c->comms[(size_t)k],
                                              q->stream);
         if (r != ncclSuccess) {
             (void)ncclGroupEnd();
@@ -143,7 +143,7 @@ static void host_coll_thread(dpg_ctx::HostColl* hp, int device, dpg_coll_ops ops
         if (!bad && ops.allreduce_sum_f64(ops.user, h.buf.p, (int64_t)h.count)) bad = 1;
         if (bad) h.failed.store(1);
         std::atomic_thread_fence(std::memory_order_release);   // the sum before the tag
-        __atomic_store_n(h.flag, job.first, __ATOMIC_RELEASE);
+        __atomic_store_n(h.flag.p, job.first, __ATOMIC_RELEASE);
         {
             std::lock_guard<std::mutex> lk(h.mu);
             ++h.done;
@@ -154,11 +154,9 @@ static void host_coll_thread(dpg_ctx::HostColl* hp, int device, dpg_coll_ops ops
 
 int dpg_ctx::HostColl::create(const dpg_ctx* c, std::unique_ptr<HostColl>& out) {
     std::unique_ptr<HostColl> h(new HostColl());
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->flag), 2 * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
-    h->flag[0] = 0;
-    h->flag[1] = 0;
-    h->timed_out = h->flag + 1;
-    for (auto& e : h->ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    if (h->flag.reserve(2) || h->ev[0].ensure(hipEventDisableTiming) || h->ev[1].ensure(hipEventDisableTiming))
+        return fail(DPG_ERR_HIP, "the collective thread's flag words and events could not be created");
+    h->flag.p[0] = h->flag.p[1] = 0;
     h->th = std::thread(host_coll_thread, h.get(), c->device, c->host_ops);
     out = std::move(h);
     return DPG_OK;
@@ -171,13 +169,11 @@ dpg_ctx::HostColl::~HostColl() {
     }
     cv.notify_all();
     if (th.joinable()) th.join();
-    if (flag) (void)hipHostFree(flag);
-    for (auto& e : ev) if (e) (void)hipEventDestroy(e);
 }
 
 // queue iteration's all-reduce on the collective thread and make the stream wait for it
 static int coll_sum_hb_host_async(dpg_ctx* c) {
-    const size_t count = (size_t)dpg_gn_dev_hb_size(&c->gn);
+    const size_t count = (size_t)dpg_gn_dev_hb_size(&c->gn.v);
     HIP_TRY(hipSetDevice(c->device));
     int rc;
     if (!c->hc && (rc = dpg_ctx::HostColl::create(c, c->hc))) return rc;
@@ -186,8 +182,8 @@ static int coll_sum_hb_host_async(dpg_ctx* c) {
     if (h.buf.cap < count && h.buf.reserve(count)) return fail(DPG_ERR_HIP, "hipHostMalloc(collective buffer) failed");
     h.count = count;
     const uint32_t tag = ++h.next_tag;
-    hipEvent_t ev = h.ev[tag & 1];
-    HIP_TRY(hipMemcpyAsync(h.buf.p, c->gn.hb_part, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
+    hipEvent_t ev = h.ev[tag & 1].e;
+    HIP_TRY(hipMemcpyAsync(h.buf.p, c->gn.v.hb_part, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipEventRecord(ev, c->stream));
     {
         std::lock_guard<std::mutex> lk(h.mu);
@@ -195,9 +191,9 @@ static int coll_sum_hb_host_async(dpg_ctx* c) {
         ++h.posted;
     }
     h.cv.notify_all();
-    rc = dpg_launch_host_wait(h.flag, tag, h.timed_out, c->stream);
+    rc = dpg_launch_host_wait(h.flag.p, tag, h.flag.p + 1, c->stream);
     if (rc) return fail(rc, "host-collective wait launch failed");
-    HIP_TRY(hipMemcpyAsync(c->gn.hb_own, h.buf.p, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->gn.v.hb_own, h.buf.p, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
     return DPG_OK;
 }
 
@@ -209,12 +205,11 @@ static void hc_drain(dpg_ctx* c) {
 }
 
 static int ensure_pipe(dpg_ctx* q) {
-    if (q->pipe_ctl) return DPG_OK;
+    if (q->pipe_slot.p) return DPG_OK;   // (made last)
     HIP_TRY(hipSetDevice(q->device));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&q->pipe_ctl), sizeof(dpg_gn_ctl)));
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&q->pipe_slot), 3 * sizeof(dpg_gn_slot),   // + [2]: the initial error
-                          hipHostMallocMapped | hipHostMallocCoherent));
-    memset(q->pipe_slot, 0, 3 * sizeof(dpg_gn_slot));
+    if (q->pipe_ctl.reserve(1) || q->pipe_slot.reserve(3))   // + [2]: the initial error
+        return fail(DPG_ERR_HIP, "GN pipeline: allocating the control block and report slots failed");
+    memset(q->pipe_slot.p, 0, 3 * sizeof(dpg_gn_slot));
     return DPG_OK;
 }
 
@@ -256,7 +251,7 @@ static int gn_loop_pipe(dpg_ctx* c, const dpg_gn_params& P, dpg_gn_stats& S, dou
     if (c->coll == kCollHost && c->hc) {   // nothing of this loop left on the collective thread
         hc_drain(c);
         if (!rc && c->hc->failed.exchange(0)) rc = fail(DPG_ERR_HIP, "the caller's all-reduce of the packed system failed");
-        if (!rc && __atomic_load_n(c->hc->timed_out, __ATOMIC_ACQUIRE))
+        if (!rc && __atomic_load_n(c->hc->flag.p + 1, __ATOMIC_ACQUIRE))
             rc = fail(DPG_ERR_HIP, "GN pipeline: no all-reduce from the collective thread in 120 s");
     }
     return rc;
@@ -269,8 +264,8 @@ static int gn_loop_pipe_body(dpg_ctx* c, const dpg_gn_params& P, dpg_gn_stats& S
         dpg_ctx* q = dev_ctx(c, k);
         if ((rc = ensure_pipe(q))) return rc;
         ++q->pipe_loop;
-        const double* cur_dev = q->gn.hb_own + 9 * q->gn.nnzb_upper + 3 * q->gn.n_nodes;   // the assembled error
-        if ((rc = dpg_gn_pipe_init(&q->gn, &P, q->pipe_ctl, cur_dev, q->pipe_slot + 2, q->pipe_loop, q->stream)))
+        const double* cur_dev = q->gn.v.hb_own + 9 * q->gn.v.nnzb_upper + 3 * q->gn.v.n_nodes;   // the assembled error
+        if ((rc = dpg_gn_pipe_init(&q->gn.v, &P, q->pipe_ctl.p, cur_dev, q->pipe_slot.p + 2, q->pipe_loop, q->stream)))
             return fail(rc, "GN pipeline launch failed");
     }
     auto issue = [&](int i) -> int {   // iteration i (1-based) reports into slot i & 1
@@ -278,14 +273,14 @@ static int gn_loop_pipe_body(dpg_ctx* c, const dpg_gn_params& P, dpg_gn_stats& S
         for (int k = 0; k < L; ++k) {
             dpg_ctx* q = dev_ctx(c, k);
             HIP_TRY(hipSetDevice(q->device));
-            if ((r = dpg_gn_pipe_issue_solve(&q->gn, q->pipe_ctl, part, q->stream)))
+            if ((r = dpg_gn_pipe_issue_solve(&q->gn.v, q->pipe_ctl.p, part, q->stream)))
                 return fail(r, "GN pipeline launch failed: %s", hipGetErrorString(hipGetLastError()));
         }
         if (part && (r = (c->coll == kCollHost ? coll_sum_hb_host_async(c) : coll_sum_hb(c)))) return r;
         for (int k = 0; k < L; ++k) {
             dpg_ctx* q = dev_ctx(c, k);
             HIP_TRY(hipSetDevice(q->device));
-            if ((r = dpg_gn_pipe_issue_ctl(&q->gn, &P, q->pipe_ctl, q->pipe_slot + (i & 1), part, q->stream)))
+            if ((r = dpg_gn_pipe_issue_ctl(&q->gn.v, &P, q->pipe_ctl.p, q->pipe_slot.p + (i & 1), part, q->stream)))
                 return fail(r, "GN pipeline launch failed: %s", hipGetErrorString(hipGetLastError()));
         }
         return DPG_OK;
@@ -293,7 +288,7 @@ static int gn_loop_pipe_body(dpg_ctx* c, const dpg_gn_params& P, dpg_gn_stats& S
     if ((rc = issue(1))) return rc;
     int issued = 1;
     std::vector<int> nfact((size_t)L, 0), reuse_last((size_t)L, 0);
-    for (int k = 0; k < L; ++k) reuse_last[(size_t)k] = dev_ctx(c, k)->gn.last_was_chord;
+    for (int k = 0; k < L; ++k) reuse_last[(size_t)k] = dev_ctx(c, k)->gn.v.last_was_chord;
     for (int i = 1;; ++i) {
         if (issued < P.max_iterations) {
             if ((rc = issue(i + 1))) return rc;
@@ -304,8 +299,8 @@ static int gn_loop_pipe_body(dpg_ctx* c, const dpg_gn_params& P, dpg_gn_stats& S
             dpg_ctx* q = dev_ctx(c, k);
             HIP_TRY(hipSetDevice(q->device));
             if (i == 1) {   // the initial error, as the device read it (pipe_init_kernel)
-                if ((rc = wait_slot(q, q->pipe_slot + 2, (uint64_t)q->pipe_loop << 32))) return rc;
-                const double e0 = static_cast<const volatile dpg_gn_slot*>(q->pipe_slot + 2)->error;
+                if ((rc = wait_slot(q, q->pipe_slot.p + 2, (uint64_t)q->pipe_loop << 32))) return rc;
+                const double e0 = static_cast<const volatile dpg_gn_slot*>(q->pipe_slot.p + 2)->error;
                 if (e0 <= 0.0) {   // nothing to do: no iteration runs (pipe_init_kernel's test, NaN runs)
                     for (int j = 0; j < L; ++j) (void)hipStreamSynchronize(dev_ctx(c, j)->stream);
                     S.initial_error = e0;
@@ -316,10 +311,10 @@ static int gn_loop_pipe_body(dpg_ctx* c, const dpg_gn_params& P, dpg_gn_stats& S
                     return DPG_OK;
                 }
             }
-            if ((rc = wait_slot(q, q->pipe_slot + (i & 1), ((uint64_t)q->pipe_loop << 32) | (uint32_t)i))) return rc;
+            if ((rc = wait_slot(q, q->pipe_slot.p + (i & 1), ((uint64_t)q->pipe_loop << 32) | (uint32_t)i))) return rc;
             dpg_gn_slot o;   // host-mapped, written by the device: read through volatile
             {
-                const volatile dpg_gn_slot* v = q->pipe_slot + (i & 1);
+                const volatile dpg_gn_slot* v = q->pipe_slot.p + (i & 1);
                 o.dinf = v->dinf;
                 o.error = v->error;
                 o.status = v->status;
@@ -328,7 +323,7 @@ static int gn_loop_pipe_body(dpg_ctx* c, const dpg_gn_params& P, dpg_gn_stats& S
                 o.final_ = v->final_;
                 o.it = v->it;
             }
-            if (i == 1 && k == 0) S.initial_error = static_cast<const volatile dpg_gn_slot*>(q->pipe_slot + 2)->error;
+            if (i == 1 && k == 0) S.initial_error = static_cast<const volatile dpg_gn_slot*>(q->pipe_slot.p + 2)->error;
             if (!o.active || o.it != i) return fail(DPG_ERR_STATE, "GN pipeline out of step (device %d, iteration %d)", k, i);
             if (k == 0) {
                 o0 = o;
@@ -339,8 +334,8 @@ static int gn_loop_pipe_body(dpg_ctx* c, const dpg_gn_params& P, dpg_gn_stats& S
                             "device 0: %.17g %.17g)", i, k, o.dinf, o.error, o0.dinf, o0.error);
             }
             if (!o.reuse) ++nfact[(size_t)k];
-            q->gn.prev_delta_inf = q->gn.last_delta_inf;
-            q->gn.last_delta_inf = o.dinf;
+            q->gn.v.prev_delta_inf = q->gn.v.last_delta_inf;
+            q->gn.v.last_delta_inf = o.dinf;
             reuse_last[(size_t)k] = o.reuse;
         }
         if (c->hc && c->hc->failed.load()) {   // the caller's collective failed: the report is not a sum
@@ -360,7 +355,7 @@ static int gn_loop_pipe_body(dpg_ctx* c, const dpg_gn_params& P, dpg_gn_stats& S
     }
     // the host bookkeeping the step API continues from (as after the host loop)
     for (int k = 0; k < L; ++k) {
-        dpg_gn_dev* g = &dev_ctx(c, k)->gn;
+        dpg_gn_dev* g = &dev_ctx(c, k)->gn.v;
         g->last_was_chord = reuse_last[(size_t)k];
         g->have_factor = 1;
         g->n_factorizations += nfact[(size_t)k];
@@ -374,7 +369,7 @@ static int gn_loop_pipe_body(dpg_ctx* c, const dpg_gn_params& P, dpg_gn_stats& S
 static bool pipe_ok(dpg_ctx* c, const dpg_gn_params& P) {
     if (P.linear_solver != DPG_SOLVER_CHOLESKY) return false;
     for (int k = 0; k < n_dev(c); ++k) {
-        const dpg_gn_dev& g = dev_ctx(c, k)->gn;
+        const dpg_gn_dev& g = dev_ctx(c, k)->gn.v;
         if (!g.chol || !dpg_chol_gated_ok(g.chol)) return false;
     }
     return true;
@@ -395,8 +390,8 @@ int gn_loop(dpg_ctx* c, const dpg_gn_params& P, double* poses, double t0, double
     for (int k = 0; k < L; ++k) {
         dpg_ctx* q = dev_ctx(c, k);
         HIP_TRY(hipSetDevice(q->device));
-        if (multi) rc = dpg_gn_dev_assemble_part(&q->gn, nullptr, q->stream);
-        else rc = dpg_gn_dev_assemble(&q->gn, q->gn.hb_own, q->stream);
+        if (multi) rc = dpg_gn_dev_assemble_part(&q->gn.v, nullptr, q->stream);
+        else rc = dpg_gn_dev_assemble(&q->gn.v, q->gn.v.hb_own, q->stream);
         if (rc) return fail(rc, "assembly launch failed");
     }
     if (multi && (rc = coll_sum_hb(c))) return rc;
@@ -415,8 +410,8 @@ int gn_loop(dpg_ctx* c, const dpg_gn_params& P, double* poses, double t0, double
                 dpg_ctx* q = dev_ctx(c, k);
                 HIP_TRY(hipSetDevice(q->device));
                 if ((rc = solve_retract_async_1(q, nullptr))) return rc;
-                if (multi) rc = dpg_gn_dev_assemble_part(&q->gn, nullptr, q->stream);
-                else rc = dpg_gn_dev_assemble(&q->gn, q->gn.hb_own, q->stream);
+                if (multi) rc = dpg_gn_dev_assemble_part(&q->gn.v, nullptr, q->stream);
+                else rc = dpg_gn_dev_assemble(&q->gn.v, q->gn.v.hb_own, q->stream);
                 if (rc) return fail(rc, "assembly launch failed");
             }
             if (multi && (rc = coll_sum_hb(c))) return rc;
@@ -435,11 +430,11 @@ int gn_loop(dpg_ctx* c, const dpg_gn_params& P, double* poses, double t0, double
             // world > 1: decide from the all-reduced vote words (every rank's max |delta| and
             // status of this iteration, dpg_gn.hip chi2_kernel), never from the local scalars
             // alone -- ranks that disagreed would issue different numbers of all-reduces and hang
-            if (multi && c->gn.n_vote > 0) {
-                const int W = c->gn.world;
+            if (multi && c->gn.v.n_vote > 0) {
+                const int W = c->gn.v.world;
                 std::vector<double> vw((size_t)(2 * W));
                 HIP_TRY(hipSetDevice(c->device));
-                HIP_TRY(hipMemcpyAsync(vw.data(), c->gn.hb_own + dpg_gn_dev_vote_offset(&c->gn), sizeof(double) * vw.size(),
+                HIP_TRY(hipMemcpyAsync(vw.data(), c->gn.v.hb_own + dpg_gn_dev_vote_offset(&c->gn.v), sizeof(double) * vw.size(),
                                        hipMemcpyDeviceToHost, c->stream));
                 HIP_TRY(hipStreamSynchronize(c->stream));
                 for (int r = 0; r < W; ++r) {
@@ -451,7 +446,7 @@ int gn_loop(dpg_ctx* c, const dpg_gn_params& P, double* poses, double t0, double
                 sc0[0] = vw[0];
             }
             if (sc0[2] != 0.0) return fail(DPG_ERR_NUMERIC, "Cholesky failed (status %d)", (int)sc0[2]);
-            S.pcg_iterations += c->gn.last_pcg_iters;
+            S.pcg_iterations += c->gn.v.last_pcg_iters;
             ++it;
             dinf = sc0[0];
             nw = sc0[1];
@@ -490,7 +485,7 @@ int gn_loop(dpg_ctx* c, const dpg_gn_params& P, double* poses, double t0, double
 static int gn_marginals_state(dpg_ctx* c, const char* fn) {
     if (!c || !c->gn_ready) return fail(DPG_ERR_STATE, "%s: graph not set up", fn);
     if (is_multi(c)) return fail(DPG_ERR_STATE, "%s: marginals are single-device (this context has several ranks)", fn);
-    if (c->gp.linear_solver != DPG_SOLVER_CHOLESKY || !c->gn.chol)
+    if (c->gp.linear_solver != DPG_SOLVER_CHOLESKY || !c->gn.v.chol)
         return fail(DPG_ERR_STATE, "%s: the graph has no Cholesky factorization (linear_solver)", fn);
     return DPG_OK;
 }
@@ -499,13 +494,13 @@ static int gn_marginals_state(dpg_ctx* c, const char* fn) {
 // factor (timed: ev[3] .. ev[4] the assembly, ev[4] .. ev[5] the factorization)
 static int gn_factor_at_current_poses(dpg_ctx* c, const char* fn, bool timed) {
     HIP_TRY(hipSetDevice(c->device));
-    dpg_gn_dev* g = &c->gn;
+    dpg_gn_dev* g = &c->gn.v;
     int rc;
-    if (timed) HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+    if (timed) HIP_TRY(hipEventRecord(c->ev[3].e, c->stream));
     if ((rc = dpg_gn_dev_assemble(g, g->hb_own, c->stream))) return fail(rc, "%s: assembly launch failed", fn);
-    if (timed) HIP_TRY(hipEventRecord(c->ev[4], c->stream));
+    if (timed) HIP_TRY(hipEventRecord(c->ev[4].e, c->stream));
     if ((rc = dpg_chol_solve(g->chol, g->hb_own, c->stream))) return fail(rc, "%s: factorization launch failed", fn);
-    if (timed) HIP_TRY(hipEventRecord(c->ev[5], c->stream));
+    if (timed) HIP_TRY(hipEventRecord(c->ev[5].e, c->stream));
     return DPG_OK;
 }
 
@@ -514,16 +509,16 @@ static int gn_marginals_blocks(dpg_ctx* c, const char* fn, const int32_t* nodes,
     int rc = gn_marginals_state(c, fn);
     if (rc) return rc;
     if (!out || n < 0 || n_pairs < 0) return fail(DPG_ERR_ARG, "%s: bad arguments", fn);
-    if (dpg_chol_selinv_check(c->gn.chol, nodes, n, pairs, n_pairs))
+    if (dpg_chol_selinv_check(c->gn.v.chol, nodes, n, pairs, n_pairs))
         return fail(DPG_ERR_ARG, "%s: a node is out of range or a pair's block is outside the factor's pattern", fn);
     if ((rc = gn_factor_at_current_poses(c, fn, ms != nullptr))) return rc;
-    rc = dpg_chol_marginals(c->gn.chol, nodes, n, pairs, n_pairs, out, c->stream);
+    rc = dpg_chol_marginals(c->gn.v.chol, nodes, n, pairs, n_pairs, out, c->stream);
     if (rc == DPG_ERR_NUMERIC) return fail(rc, "%s: H is not positive definite", fn);
     if (rc) return fail(rc, "%s: selected inversion failed", fn);
     if (ms) {
         float a = 0.f, f = 0.f;
-        HIP_TRY(hipEventElapsedTime(&a, c->ev[3], c->ev[4]));
-        HIP_TRY(hipEventElapsedTime(&f, c->ev[4], c->ev[5]));
+        HIP_TRY(hipEventElapsedTime(&a, c->ev[3].e, c->ev[4].e));
+        HIP_TRY(hipEventElapsedTime(&f, c->ev[4].e, c->ev[5].e));
         ms[0] = a;
         ms[1] = f;
     }
@@ -533,7 +528,7 @@ static int gn_marginals_blocks(dpg_ctx* c, const char* fn, const int32_t* nodes,
 // the pairs must share a factor (H's own pattern): blocks that only fill or a relaxed supernode put
 // into L's pattern are not part of the interface
 static int gn_pairs_share_factor(dpg_ctx* c, const int32_t* pairs, int64_t n) {
-    const dpg_gn_dev& g = c->gn;
+    const dpg_gn_dev& g = c->gn.v;
     if (!c->gn_pairs_valid) {
         HIP_TRY(hipSetDevice(c->device));
         std::vector<dpg_factor> F((size_t)g.n_factors);
@@ -569,10 +564,10 @@ static int gn_joint_blocks(dpg_ctx* c, const char* fn, int by_nodes, const int32
     if (rc) return rc;
     if (n < 0 || (n > 0 && (!idx || !out))) return fail(DPG_ERR_ARG, "%s: bad arguments", fn);
     for (int64_t q = 0, e = by_nodes ? n : 2 * n; q < e; ++q)
-        if (idx[q] < 0 || idx[q] >= c->gn.n_nodes) return fail(DPG_ERR_ARG, "%s: node %d is out of range", fn, idx[q]);
+        if (idx[q] < 0 || idx[q] >= c->gn.v.n_nodes) return fail(DPG_ERR_ARG, "%s: node %d is out of range", fn, idx[q]);
     if (n == 0) return DPG_OK;
     if ((rc = gn_factor_at_current_poses(c, fn, false))) return rc;
-    rc = dpg_chol_joint(c->gn.chol, by_nodes, idx, n, out, c->stream, ms);
+    rc = dpg_chol_joint(c->gn.v.chol, by_nodes, idx, n, out, c->stream, ms);
     if (rc == DPG_ERR_NUMERIC) return fail(rc, "%s: H is not positive definite", fn);
     if (rc) return fail(rc, "%s: the path solve failed", fn);
     return DPG_OK;
@@ -606,7 +601,7 @@ int dpg_gn_take_icp_measurements(dpg_ctx* c, int64_t first, int64_t count, int64
                  ith = 1.0 / (double)p->laser_theta_variance;
     if (!is_multi(c)) {
         if (count > c->n_edges) return fail(DPG_ERR_ARG, "only %lld ICP results available", (long long)c->n_edges);
-        int rc = dpg_gn_dev_icp_to_factors(&c->gn, c->res.p, first, count, n_always, ix, iy, ith, c->stream);
+        int rc = dpg_gn_dev_icp_to_factors(&c->gn.v, c->res.p, first, count, n_always, ix, iy, ith, c->stream);
         return rc ? fail(rc, "dpg_gn_take_icp_measurements failed") : DPG_OK;
     }
     // every slot of the batch: the aligning device's result, on that device only
@@ -616,9 +611,9 @@ int dpg_gn_take_icp_measurements(dpg_ctx* c, int64_t first, int64_t count, int64
     for (int k = 0; k < n_dev(c); ++k) {
         dpg_ctx* q = dev_ctx(c, k);
         HIP_TRY(hipSetDevice(q->device));
-        if (!q->gn_ready || !q->gn.mine) return fail(DPG_ERR_STATE, "graph not set up on device %d", k);
+        if (!q->gn_ready || !q->gn.v.mine) return fail(DPG_ERR_STATE, "graph not set up on device %d", k);
         const int64_t nl = (int64_t)c->shard[(size_t)k].size();
-        const int rc = dpg_gn_dev_icp_to_factors_scatter(&q->gn, q->res.p, q->shard_idx.p, nl, first, count, n_always,
+        const int rc = dpg_gn_dev_icp_to_factors_scatter(&q->gn.v, q->res.p, q->shard_idx.p, nl, first, count, n_always,
                                                          ix, iy, ith, q->stream);
         if (rc) return fail(rc, "dpg_gn_take_icp_measurements failed");
     }
@@ -626,11 +621,11 @@ int dpg_gn_take_icp_measurements(dpg_ctx* c, int64_t first, int64_t count, int64
     return DPG_OK;
 }
 
-int64_t dpg_gn_hb_size(dpg_ctx* c) { return (c && c->gn_ready) ? dpg_gn_dev_hb_size(&c->gn) : -1; }
+int64_t dpg_gn_hb_size(dpg_ctx* c) { return (c && c->gn_ready) ? dpg_gn_dev_hb_size(&c->gn.v) : -1; }
 
 int dpg_gn_setup_profile(dpg_ctx* c, double out[5]) {
     if (!c || !c->gn_ready || !out) return fail(DPG_ERR_STATE, "graph not set up");
-    for (int k = 0; k < 5; ++k) out[k] = c->gn.setup_ms[k];
+    for (int k = 0; k < 5; ++k) out[k] = c->gn.v.setup_ms[k];
     return DPG_OK;
 }
 
@@ -647,7 +642,7 @@ int dpg_gn_set_poses(dpg_ctx* c, const double* poses) {
 int dpg_gn_get_poses(dpg_ctx* c, double* poses) {
     if (!c || !c->gn_ready || !poses) return fail(DPG_ERR_STATE, "graph not set up");
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpyAsync(poses, c->gn.poses, sizeof(double) * 3 * (size_t)c->gn.n_nodes, hipMemcpyDeviceToHost,
+    HIP_TRY(hipMemcpyAsync(poses, c->gn.v.poses, sizeof(double) * 3 * (size_t)c->gn.v.n_nodes, hipMemcpyDeviceToHost,
                            c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return DPG_OK;
@@ -655,24 +650,24 @@ int dpg_gn_get_poses(dpg_ctx* c, double* poses) {
 
 int dpg_gn_assemble(dpg_ctx* c, double* hb_dev) {
     DPG_STEP_API_1(c);
-    if (!hb_dev) hb_dev = c->gn.hb_own;
-    HIP_TRY(hipEventRecord(c->ev[3], c->stream));
-    int rc = dpg_gn_dev_assemble(&c->gn, hb_dev, c->stream);
+    if (!hb_dev) hb_dev = c->gn.v.hb_own;
+    HIP_TRY(hipEventRecord(c->ev[3].e, c->stream));
+    int rc = dpg_gn_dev_assemble(&c->gn.v, hb_dev, c->stream);
     if (rc) return fail(rc, "assembly launch failed");
-    HIP_TRY(hipEventRecord(c->ev[4], c->stream));
+    HIP_TRY(hipEventRecord(c->ev[4].e, c->stream));
     return DPG_OK;
 }
 
 int dpg_gn_solve_retract(dpg_ctx* c, const double* hb_dev, double* delta_inf, double* error, int32_t* pcg_iters) {
     DPG_STEP_API_1(c);
-    if (!hb_dev) hb_dev = c->gn.hb_own;
-    int rc = dpg_gn_dev_solve(&c->gn, hb_dev, &c->gp, c->stream, delta_inf, error, pcg_iters);
+    if (!hb_dev) hb_dev = c->gn.v.hb_own;
+    int rc = dpg_gn_dev_solve(&c->gn.v, hb_dev, &c->gp, c->stream, delta_inf, error, pcg_iters);
     if (rc) return fail(rc, "PCG solve failed: %s", hipGetErrorString(hipGetLastError()));
-    HIP_TRY(hipEventRecord(c->ev[5], c->stream));
+    HIP_TRY(hipEventRecord(c->ev[5].e, c->stream));
     float a = 0.f, s = 0.f;
-    if (hipEventSynchronize(c->ev[5]) == hipSuccess) {
-        (void)hipEventElapsedTime(&a, c->ev[3], c->ev[4]);
-        (void)hipEventElapsedTime(&s, c->ev[4], c->ev[5]);
+    if (hipEventSynchronize(c->ev[5].e) == hipSuccess) {
+        (void)hipEventElapsedTime(&a, c->ev[3].e, c->ev[4].e);
+        (void)hipEventElapsedTime(&s, c->ev[4].e, c->ev[5].e);
     }
     c->asm_ms = a;
     c->solve_ms = s;
@@ -684,7 +679,7 @@ int dpg_gn_solve_retract_async(dpg_ctx* c, const double* hb_dev) {
     return solve_retract_async_1(c, hb_dev);
 }
 
-int32_t dpg_gn_factorizations(dpg_ctx* c) { return (c && c->gn_ready) ? c->gn.n_factorizations : -1; }
+int32_t dpg_gn_factorizations(dpg_ctx* c) { return (c && c->gn_ready) ? c->gn.v.n_factorizations : -1; }
 
 int dpg_gn_fetch(dpg_ctx* c, const double* hb_dev, double out[3]) {
     DPG_STEP_API_1(c);
@@ -718,8 +713,8 @@ int dpg_optimize_graph(dpg_ctx* c, double* poses, int64_t V, const dpg_factor* F
 }
 
 int dpg_gn_marginals(dpg_ctx* c, const int32_t* nodes, int64_t n, double* cov_out) {
-    if (c && c->gn_ready && !nodes && n != c->gn.n_nodes)
-        return fail(DPG_ERR_ARG, "dpg_gn_marginals: nodes == NULL asks for every node (n = %lld)", (long long)c->gn.n_nodes);
+    if (c && c->gn_ready && !nodes && n != c->gn.v.n_nodes)
+        return fail(DPG_ERR_ARG, "dpg_gn_marginals: nodes == NULL asks for every node (n = %lld)", (long long)c->gn.v.n_nodes);
     return gn_marginals_blocks(c, "dpg_gn_marginals", nodes, n, nullptr, 0, cov_out, nullptr);
 }
 
@@ -747,10 +742,10 @@ int dpg_gn_relative_covariances(dpg_ctx* c, const int32_t* pairs, int64_t n, dou
     if (n < 0 || (n > 0 && (!pairs || !cov_out))) return fail(DPG_ERR_ARG, "%s: bad arguments", fn);
     if (n == 0) return DPG_OK;
     for (int64_t q = 0; q < 2 * n; ++q)
-        if (pairs[q] < 0 || pairs[q] >= c->gn.n_nodes) return fail(DPG_ERR_ARG, "%s: node %d is out of range", fn, pairs[q]);
+        if (pairs[q] < 0 || pairs[q] >= c->gn.v.n_nodes) return fail(DPG_ERR_ARG, "%s: node %d is out of range", fn, pairs[q]);
     std::vector<int32_t> tri((size_t)(6 * n));
     dpg_relative_triples(pairs, n, tri.data());
-    std::vector<double> blocks((size_t)(27 * n)), X((size_t)(3 * c->gn.n_nodes));
+    std::vector<double> blocks((size_t)(27 * n)), X((size_t)(3 * c->gn.v.n_nodes));
     if ((rc = gn_joint_blocks(c, fn, 0, tri.data(), 3 * n, blocks.data(), nullptr))) return rc;
     if ((rc = dpg_gn_get_poses(c, X.data()))) return rc;
     dpg_relative_from_blocks(pairs, n, X.data(), blocks.data(), cov_out);
@@ -766,7 +761,7 @@ int dpg_gn_joint_profile(dpg_ctx* c, const int32_t* pairs, int64_t n, double* ou
     const int rc = gn_joint_blocks(c, "dpg_gn_joint_profile", 0, pairs, n, cov.data(), ms);
     if (rc) return rc;
     int64_t st[2];
-    dpg_chol_path_stats(c->gn.chol, st);
+    dpg_chol_path_stats(c->gn.v.chol, st);
     out[0] = ms[0];
     out[1] = ms[1];
     out[2] = (double)st[0];
@@ -794,19 +789,19 @@ int64_t dpg_gn_marginals_profile(dpg_ctx* c, double* out, int64_t cap) {
     int rc = gn_marginals_state(c, "dpg_gn_marginals_profile");
     if (rc) return rc;
     if (!out || cap < 4) return fail(DPG_ERR_ARG, "dpg_gn_marginals_profile: bad arguments");
-    std::vector<double> cov((size_t)(9 * c->gn.n_nodes));
+    std::vector<double> cov((size_t)(9 * c->gn.v.n_nodes));
     double ms[2];
-    if ((rc = gn_marginals_blocks(c, "dpg_gn_marginals_profile", nullptr, c->gn.n_nodes, nullptr, 0, cov.data(), ms)))
+    if ((rc = gn_marginals_blocks(c, "dpg_gn_marginals_profile", nullptr, c->gn.v.n_nodes, nullptr, 0, cov.data(), ms)))
         return rc;
     double st[6];
-    dpg_chol_stats(c->gn.chol, st);
+    dpg_chol_stats(c->gn.v.chol, st);
     const int nl = (int)st[1];
     std::vector<float> lv((size_t)nl, 0.f);
-    if ((rc = dpg_chol_selinv_timed(c->gn.chol, c->stream, lv.data(), nl))) return fail(rc, "selected inversion failed");
+    if ((rc = dpg_chol_selinv_timed(c->gn.v.chol, c->stream, lv.data(), nl))) return fail(rc, "selected inversion failed");
     out[0] = ms[0];
     out[1] = ms[1];
     out[2] = nl;
-    out[3] = (double)dpg_chol_selinv_bytes(c->gn.chol);
+    out[3] = (double)dpg_chol_selinv_bytes(c->gn.v.chol);
     int64_t k = 4;
     for (int q = 0; q < nl && k < cap; ++q) out[k++] = lv[(size_t)q];
     return k;

@@ -374,6 +374,34 @@ void dpg_relative_from_blocks(const int32_t* pairs, int64_t n, const double* X, 
     }
 }
 
+/* Contribution lists per upper block (lin_gather_kernel walks them), in factor order: count, exclusive
+ * scan, fill with cptr[u] as block u's cursor -- which leaves every offset one block ahead -- then shift back. */
+void dpg_contribution_lists(const dpg_factor* F, int64_t nf, int64_t n, const int32_t* pair, int64_t n_pairs,
+                            int32_t* cptr, int32_t* clist) {
+    const int64_t nu = n + n_pairs;
+    memset(cptr, 0, (size_t)(nu + 1) * sizeof(int32_t));
+    for (int64_t k = 0; k < nf; ++k) {
+        const int32_t i = F[k].i, j = F[k].j;
+        cptr[i]++;
+        if (F[k].kind == DPG_FACTOR_BETWEEN) {
+            cptr[j]++;
+            cptr[n + pair[k]]++;
+        }
+    }
+    int32_t at = 0;   /* (kept in a register: a sum carried through cptr itself is several times slower) */
+    for (int64_t u = 0; u <= nu; ++u) { const int32_t c = cptr[u]; cptr[u] = at; at += c; }
+    for (int64_t k = 0; k < nf; ++k) {
+        const int32_t i = F[k].i, j = F[k].j;
+        clist[cptr[i]++] = (int32_t)(k << 2 | 0);
+        if (F[k].kind == DPG_FACTOR_BETWEEN) {
+            clist[cptr[j]++] = (int32_t)(k << 2 | 1);
+            clist[cptr[n + pair[k]]++] = (int32_t)(k << 2 | (i < j ? 2 : 3));
+        }
+    }
+    memmove(cptr + 1, cptr, (size_t)nu * sizeof(int32_t));
+    cptr[0] = 0;
+}
+
 static void sym6(double* m, int i, int j, double v) { m[6 * i + j] = v; m[6 * j + i] = v; }
 static void swap_d(double* a, double* b) { const double t = *a; *a = *b; *b = t; }
 

@@ -67,7 +67,7 @@ int launch_batch(dpg_ctx* c, const ScanView& v, const dpg_icp_edge* edges_dev, i
         return fail(DPG_ERR_SIZE, "downsampled cloud of %d points: only the angular ICP variant takes more than 4096", maxp);
     int rc = join_cov(c);
     if (rc) return fail(rc, "stream wait failed");
-    if (timed) HIP_TRY(hipEventRecord(c->ev[6], c->stream));
+    if (timed) HIP_TRY(hipEventRecord(c->ev[6].e, c->stream));
     if (c->icp_variant == DPG_ICP_KDTREE) {
         rc = dpg_launch_kdtree_build(v.ds, v.ds_off, v.n_nodes, v.max_pts, v.idx_pts, v.idx_ids, c->stream);
         if (rc) return fail(rc, "k-d tree build launch failed (%d)", rc);
@@ -79,7 +79,7 @@ int launch_batch(dpg_ctx* c, const ScanView& v, const dpg_icp_edge* edges_dev, i
     }
     if (v.ds == c->ds.p)   // the store's own indexes: current for every node now, or (other variants) overwritten
         c->idx_valid = c->icp_variant != DPG_ICP_ANGULAR ? 0 : tree_from <= c->idx_valid ? v.n_nodes : c->idx_valid;
-    if (timed) HIP_TRY(hipEventRecord(c->ev[0], c->stream));
+    if (timed) HIP_TRY(hipEventRecord(c->ev[0].e, c->stream));
     if (c->icp_variant == DPG_ICP_ANGULAR) {
         kp.lds_tgt = round_up(std::max<int32_t>(maxp, 1), 16);   // record capacity
         kp.defer_cap = c->defer_cap;
@@ -103,13 +103,13 @@ int launch_batch(dpg_ctx* c, const ScanView& v, const dpg_icp_edge* edges_dev, i
         rc = dpg_launch_icp(v.ds, edges_dev, ne, &kp, maxp, res_dev, trace_dev, c->stream);
     }
     if (rc) return fail(rc, "ICP kernel launch failed (%d): %s", rc, hipGetErrorString(hipGetLastError()));
-    if (timed) HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    if (timed) HIP_TRY(hipEventRecord(c->ev[1].e, c->stream));
     if (hess_dev && timed) {   // beside the pose graph: on aux, after the ICP
-        if (!c->aux) HIP_TRY(hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking));
-        HIP_TRY(hipStreamWaitEvent(c->aux, c->ev[1], 0));
-        rc = dpg_launch_cov(v.full, edges_dev, ne, res_dev, hess_dev, c->cov_wg, c->aux);
+        if (!c->aux.s) HIP_TRY(hipStreamCreateWithFlags(&c->aux.s, hipStreamNonBlocking));
+        HIP_TRY(hipStreamWaitEvent(c->aux.s, c->ev[1].e, 0));
+        rc = dpg_launch_cov(v.full, edges_dev, ne, res_dev, hess_dev, c->cov_wg, c->aux.s);
         if (rc) return fail(rc, "covariance kernel launch failed");
-        HIP_TRY(hipEventRecord(c->ev[2], c->aux));
+        HIP_TRY(hipEventRecord(c->ev[2].e, c->aux.s));
         c->cov_pending = true;
         c->cov_on_aux = true;
         return DPG_OK;
@@ -119,7 +119,7 @@ int launch_batch(dpg_ctx* c, const ScanView& v, const dpg_icp_edge* edges_dev, i
         rc = dpg_launch_cov(v.full, edges_dev, ne, res_dev, hess_dev, 0, c->stream);
         if (rc) return fail(rc, "covariance kernel launch failed");
     }
-    if (timed) HIP_TRY(hipEventRecord(c->ev[2], c->stream));
+    if (timed) HIP_TRY(hipEventRecord(c->ev[2].e, c->stream));
     return DPG_OK;
 }
 
@@ -169,7 +169,7 @@ static int scans_upload_1(dpg_ctx* c, const float* pts, const int64_t* off, int6
     if (ratio < 1) ratio = 1;
     HIP_TRY(hipSetDevice(c->device));
     if (c->cov_pending) {   // the store may be re-allocated under a running covariance
-        HIP_TRY(hipEventSynchronize(c->ev[2]));
+        HIP_TRY(hipEventSynchronize(c->ev[2].e));
         c->cov_pending = false;
     }
     const int64_t total = off[V];
@@ -210,7 +210,7 @@ static int scans_append_1(dpg_ctx* c, const float* pts, const int64_t* off, int6
     if (c->n_nodes == 0) return scans_upload_1(c, pts, off, k, ratio);
     if (c->cov_pending) {   // the store may be re-allocated under a running covariance
         HIP_TRY(hipSetDevice(c->device));
-        HIP_TRY(hipEventSynchronize(c->ev[2]));
+        HIP_TRY(hipEventSynchronize(c->ev[2].e));
         c->cov_pending = false;
     }
     if (ratio != c->ratio) return fail(DPG_ERR_STATE, "scans were uploaded with downsample ratio %d", c->ratio);
@@ -544,8 +544,8 @@ static float batch_ms(dpg_ctx* c, int a, int b) {
     for (int k = 0; k < (c ? n_dev(c) : 0); ++k) {
         dpg_ctx* q = dev_ctx(c, k);
         float ms = -1.f;
-        if (hipSetDevice(q->device) != hipSuccess || hipEventSynchronize(q->ev[b]) != hipSuccess ||
-            hipEventElapsedTime(&ms, q->ev[a], q->ev[b]) != hipSuccess)
+        if (hipSetDevice(q->device) != hipSuccess || hipEventSynchronize(q->ev[b].e) != hipSuccess ||
+            hipEventElapsedTime(&ms, q->ev[a].e, q->ev[b].e) != hipSuccess)
             return -1.f;
         worst = std::max(worst, ms);
     }
@@ -676,8 +676,8 @@ int dpg_icp_batch_run(dpg_ctx* c, int32_t compute_cov, int32_t trace_iters) {
 
 float dpg_kdtree_build_ms(dpg_ctx* c) {
     float ms = -1.f;
-    if (!c || hipEventSynchronize(c->ev[0]) != hipSuccess) return -1.f;
-    if (hipEventElapsedTime(&ms, c->ev[6], c->ev[0]) != hipSuccess) return -1.f;
+    if (!c || hipEventSynchronize(c->ev[0].e) != hipSuccess) return -1.f;
+    if (hipEventElapsedTime(&ms, c->ev[6].e, c->ev[0].e) != hipSuccess) return -1.f;
     return ms;
 }
 

@@ -214,25 +214,7 @@ int inc_rebuild_lists(dpg_inc* q, hipStream_t s) {
     if (q->h_lists.reserve_amortised((size_t)(nu + 1 + n_list), 4096)) return DPG_ERR_HIP;
     int32_t* cnt = q->h_lists.p;
     int32_t* clist = q->h_lists.p + nu + 1;
-    std::fill(cnt, cnt + nu + 1, 0);
-    for (int64_t k = 0; k < nf; ++k) {
-        const dpg_factor& f = q->F[(size_t)k];
-        cnt[(size_t)f.i + 1]++;
-        if (f.kind == DPG_FACTOR_BETWEEN) {
-            cnt[(size_t)f.j + 1]++;
-            cnt[(size_t)(n + q->f_pair[(size_t)k]) + 1]++;
-        }
-    }
-    for (int64_t u = 0; u < nu; ++u) cnt[(size_t)u + 1] += cnt[(size_t)u];
-    std::vector<int32_t> cur(cnt, cnt + nu);
-    for (int64_t k = 0; k < nf; ++k) {
-        const dpg_factor& f = q->F[(size_t)k];
-        clist[(size_t)cur[(size_t)f.i]++] = (int32_t)(k << 2 | 0);
-        if (f.kind == DPG_FACTOR_BETWEEN) {
-            clist[(size_t)cur[(size_t)f.j]++] = (int32_t)(k << 2 | 1);
-            clist[(size_t)cur[(size_t)(n + q->f_pair[(size_t)k])]++] = (int32_t)(k << 2 | (f.i < f.j ? 2 : 3));
-        }
-    }
+    dpg_contribution_lists(q->F.data(), nf, n, q->f_pair.data(), P, cnt, clist);
     g.n_nodes = n;
     g.n_factors = nf;
     g.nnzb_upper = nu;

@@ -115,19 +115,17 @@ typedef struct dpg_csm_pair {
     int32_t pad[2];
 } dpg_csm_pair;
 
-/* Pose-graph system on device (defined in dpg_gn.hip). */
+/* Pose-graph system on device as the kernels and launchers of dpg_gn.hip see it: a view, raw
+   pointers into buffers that the batch graph (GnGraph, dpg_ctx.h) or the incremental graph
+   (dpg_inc.hip) owns. */
 typedef struct dpg_gn_dev {
     int64_t n_nodes, n_factors, nnzb_upper, nnzb_full;
     int64_t shard_begin, shard_end;
     /* factors and their per-block contribution lists */
     dpg_factor* factors;           /* [n_factors] */
     /* upper pattern: block u (0..nnzb_upper) = (row, col) with row <= col; diag blocks first */
-    int32_t* up_row;               /* [nnzb_upper] */
-    int32_t* up_col;
     int32_t* up_cptr;              /* [nnzb_upper + 1] contribution list ptr */
     int32_t* up_clist;             /* factor index << 2 | role (0: ii, 1: jj, 2: ij, 3: ji) */
-    int32_t* node_fptr;            /* [n_nodes + 1] factors whose FIRST key is the node (chi2/b) */
-    int32_t* node_flist;
     /* full BSR for the solve */
     int32_t* rowptr;               /* [n_nodes + 1] */
     int32_t* colidx;               /* [nnzb_full] */
@@ -161,7 +159,7 @@ typedef struct dpg_gn_dev {
        (dpg_gn_pipe.h): the ranks cannot disagree on the iteration count, and with it on the number
        of collectives they issue */
     int32_t n_vote;
-    /* host clock of the last dpg_gn_dev_alloc (ms): pattern + contribution lists + BSR rows, the
+    /* host clock of the batch graph's build (ms): pattern + contribution lists + BSR rows, the
        Cholesky's symbolic analysis, its host plan (these three before the stream wait), the wait +
        device allocations + uploads, the Cholesky's upload */
     double setup_ms[5];
@@ -238,11 +236,12 @@ void dpg_relative_covariance(const double xi[3], const double xj[3], const doubl
 void dpg_relative_triples(const int32_t* pairs, int64_t n, int32_t* tri);
 void dpg_relative_from_blocks(const int32_t* pairs, int64_t n, const double* X, const double* blocks, double* out);
 
-/* host work first (pattern, lists, the Cholesky's analysis and plan), then -- after
-   hipStreamSynchronize(sync_stream) when given -- the device allocations and uploads */
-int dpg_gn_dev_alloc(dpg_gn_dev* g, int64_t n_nodes, const dpg_factor* factors, int64_t n_factors,
-                     int64_t shard_begin, int64_t shard_end, const struct dpg_chol_opts* opts, void* sync_stream);
-void dpg_gn_dev_free(dpg_gn_dev* g);
+/* The contribution lists of every upper block, in factor order (dpg_host.c): block u < n is node u's diagonal
+   block, block n + p pair p's; pair[k] = the pair of Between factor k.  cptr[n + n_pairs + 1] gets the CSR offsets,
+   clist the entries factor << 2 | role (0: ii, 1: jj, 2: ij, 3: ji): one per prior, three per Between. */
+__attribute__((visibility("hidden"))) void dpg_contribution_lists(const dpg_factor* factors, int64_t n_factors, int64_t n,
+                                                                  const int32_t* pair, int64_t n_pairs, int32_t* cptr,
+                                                                  int32_t* clist);
 int64_t dpg_gn_dev_hb_size(const dpg_gn_dev* g);
 int64_t dpg_gn_dev_vote_offset(const dpg_gn_dev* g);   /* first vote word of the packed buffer */
 int dpg_gn_dev_assemble(dpg_gn_dev* g, double* hb_dev, void* stream);
@@ -256,8 +255,10 @@ int dpg_gn_dev_solve(dpg_gn_dev* g, const double* hb_dev, const dpg_gn_params* g
 int dpg_gn_dev_icp_to_factors(dpg_gn_dev* g, const dpg_icp_result* results_dev, int64_t first,
                               int64_t count, int64_t n_always, double info_x, double info_y,
                               double info_th, void* stream);
-/* multi-device forms: factor f is this device's when f mod world == rank (allocates mine + hb_part) */
-int dpg_gn_dev_set_ownership(dpg_gn_dev* g, int32_t world, int32_t rank, void* stream);
+/* multi-device forms: factor f is this device's when f mod world == rank (the owner, dpg_ctx.h,
+   allocates mine + hb_part and regrows hb_own by the vote words) */
+struct GnGraph;
+int dpg_gn_dev_set_ownership(struct GnGraph* g, int32_t world, int32_t rank, void* stream);
 /* ICP slots [first, first + count) of the batch: this device's n_local results (caller indices
    idx_dev) become its factors, every other slot in the range another device's */
 int dpg_gn_dev_icp_to_factors_scatter(dpg_gn_dev* g, const dpg_icp_result* results_dev, const int32_t* idx_dev,

@@ -194,17 +194,14 @@ int64_t dpg_get_map(dpg_ctx* c, const float* est, int32_t fraction, float* out, 
         if (dfr.reserve((size_t)(4 * V)) || dout.reserve((size_t)(2 * K)) || doff.reserve((size_t)(V + 1))) return DPG_ERR_HIP;
         HIP_TRY(hipMemcpyAsync(dfr.p, fr.data(), sizeof(float) * 4 * V, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(doff.p, c->full_off.data(), sizeof(int64_t) * (V + 1), hipMemcpyHostToDevice, c->stream));
-        if (!c->map_ev[0]) {
-            HIP_TRY(hipEventCreate(&c->map_ev[0]));
-            HIP_TRY(hipEventCreate(&c->map_ev[1]));
-        }
-        HIP_TRY(hipEventRecord(c->map_ev[0], c->stream));
+        if (c->map_ev[0].ensure(hipEventDefault) || c->map_ev[1].ensure(hipEventDefault)) return DPG_ERR_HIP;
+        HIP_TRY(hipEventRecord(c->map_ev[0].e, c->stream));
         if (dpg_launch_map_points(c->full.p, doff.p, dfr.p, V, fraction, dout.p, c->stream)) return DPG_ERR_HIP;
-        HIP_TRY(hipEventRecord(c->map_ev[1], c->stream));
+        HIP_TRY(hipEventRecord(c->map_ev[1].e, c->stream));
         HIP_TRY(hipMemcpyAsync(out, dout.p, sizeof(float) * 2 * std::min(K, cap), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         float ms = 0.f;
-        if (hipEventElapsedTime(&ms, c->map_ev[0], c->map_ev[1]) == hipSuccess) c->map_ms = ms;
+        if (hipEventElapsedTime(&ms, c->map_ev[0].e, c->map_ev[1].e) == hipSuccess) c->map_ms = ms;
         return DPG_OK;
     };
     if (assemble()) return fail(DPG_ERR_HIP, "map assembly failed: %s", hipGetErrorString(hipGetLastError()));

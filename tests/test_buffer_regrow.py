@@ -1,6 +1,6 @@
-"""Regrowth of the buffers the solver, the incremental graph and the DPG store own (csrc/dpg_buf.h:
-OwnedBuf behind DevBuf / PinBuf) while every lazily created buffer exists: results must not depend
-on how often, or in what state, an array was reallocated.
+"""Regrowth of the buffers the solver, the incremental graph, the DPG store and the context's batch
+graph own (csrc/dpg_buf.h: OwnedBuf behind DevBuf / PinBuf) while every lazily created buffer exists:
+results must not depend on how often, or in what state, an array was reallocated or a graph replaced.
 
 The incremental graph is compared with OracleIncGraph (poses, tests/test_inc.py's bound) and with the
 dense inverse of the oracle's H at the oracle's linearization points (tests/test_marginals.py's
@@ -12,6 +12,8 @@ import pytest
 
 from graphs import pose_diff
 from oracle import oracle as O
+from multi_common import perr
+from test_ctx_teardown import _two_node_graph
 from test_inc import POSE_TOL
 from test_marginals import blk, dense_reference, rel_err, rel_pose
 
@@ -158,3 +160,65 @@ def test_store_append_regrows_everything(ctx):
     finally:
         grown.close()
         whole.close()
+
+
+def _batch_graphs():
+    """(X0, F) of the two-node graph of tests/test_ctx_teardown.py, the 12-node loop chain and a three-node chain."""
+    out = [_two_node_graph()[:2]]
+    for V in (12, 3):
+        X0, by_node = _loop_chain(V)
+        out.append((X0, np.concatenate([by_node[v] for v in range(V)])))
+    return out
+
+
+def _gn(c, X0, F):
+    c.gn_setup(len(X0), F)
+    c.gn_set_poses(X0)
+    return c.gn_run(len(X0))[1]
+
+
+def test_batch_graph_replaced_on_one_context():
+    """Three graphs set up in turn on ONE context, each replacing the last (the 12-node one with the
+    solver's selected-inverse buffers alive), then a setup that fails: every graph's poses equal, byte
+    for byte, those of a fresh context given only that graph, and the failed setup leaves the
+    three-node graph live -- a run from its initial poses gives its bytes again."""
+    from dpgslam import _abi, api
+    graphs = _batch_graphs()
+    fresh = []
+    for X0, F in graphs:
+        with api.Context(0) as c:
+            fresh.append(_gn(c, X0, F).tobytes())
+    with api.Context(0) as c:
+        for (X0, F), want in zip(graphs, fresh):
+            assert _gn(c, X0, F).tobytes() == want, len(X0)
+            if len(X0) == 12:
+                assert c.gn_marginals().shape == (12, 3, 3)
+        X0, F = graphs[-1]
+        bad = api.between_factor(0, len(X0), (1.0, 0.0, 0.0), (0.1, 0.1, 0.05))   # j == V
+        with pytest.raises(_abi.DpgError, match=r"\(-1\)"):   # DPG_ERR_ARG
+            c.gn_setup(len(X0), np.concatenate([F, bad]))
+        c.gn_set_poses(X0)
+        assert c.gn_run(len(X0))[1].tobytes() == fresh[-1]
+
+
+def test_virtual_devices_graph_replaced():
+    """optimize_graph on two virtual devices for the 12-node graph, the two-node graph and the 12-node
+    graph again: every setup regrows hb_own by the vote words and makes hb_part and the ownership
+    bytes anew.  tests/test_multi_gpu_ctx.py's bar against one device (the same iteration and
+    factorization counts, poses within 1e-9); the first and the third result byte-identical."""
+    from dpgslam import api
+    two, twelve, _ = _batch_graphs()
+    ref = {}
+    for X0, F in (two, twelve):
+        with api.Context(0) as c:
+            X, st = c.optimize_graph(X0, F)
+            ref[len(X0)] = (X, st.iterations, c.gn_factorizations())
+    got = []
+    with api.Context(0, virtual=2) as c:
+        for X0, F in (twelve, two, twelve):
+            X, st = c.optimize_graph(X0, F)
+            Xr, it, nf = ref[len(X0)]
+            assert (st.iterations, c.gn_factorizations()) == (it, nf), len(X0)
+            assert perr(X, Xr) < 1e-9, (len(X0), perr(X, Xr))
+            got.append(X.tobytes())
+    assert got[0] == got[2]

@@ -72,3 +72,29 @@ def test_destroy_with_every_lazy_resource_allocated():
     with api.Context(0) as fresh:
         X, st = fresh.optimize_graph(X0, F)
         assert st.iterations > 0 and np.abs(pose_diff(X, X_opt)).max() < 1e-9, X
+
+
+@pytest.mark.gpu
+def test_destroy_virtual_context_with_every_lazy_resource(workload):
+    """Two virtual devices with everything a context makes on first use in existence: a batch with its
+    covariance on the side stream (config1), the map events (one get_map), and -- optimize_graph --
+    the pipelined loop's control block and report slots and the ownership buffers on both device
+    contexts.  The raw destroy releases all of it; a fresh context then solves as before."""
+    from dpgslam import _abi, api
+    from graphs import pose_diff
+    X0, F, X_opt = _two_node_graph()
+    w = workload("config1")
+    p = _abi.default_icp_params()
+    ctx = api.Context(0, virtual=2)
+    ctx.upload_scans(w.pts, w.offsets, p.downsample_icp_points_ratio)
+    res, hess = ctx.icp_batch(w.edges, w.est, p, compute_cov=True)
+    assert len(res) == w.E and np.isfinite(hess).all()
+    assert len(ctx.get_map(w.est)) > 0
+    X, st = ctx.optimize_graph(X0, F)
+    assert st.iterations > 0 and np.abs(pose_diff(X, X_opt)).max() < 1e-9, X
+    api.lib().dpg_ctx_destroy(ctx.handle)
+    ctx.handle = None
+    ctx.close()
+    with api.Context(0) as fresh:
+        X, st = fresh.optimize_graph(X0, F)
+        assert st.iterations > 0 and np.abs(pose_diff(X, X_opt)).max() < 1e-9, X

@@ -15,4 +15,4 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_host_code_under_asan_ubsan():
     r = subprocess.run(["make", "-C", os.path.join(ROOT, "oracle"), "sanitize"], capture_output=True, text=True,
                        timeout=600)
-    assert r.returncode == 0 and "sanitize check ok" in r.stdout and "solver plans ok" in r.stdout and "buffers ok" in r.stdout, (r.stdout + r.stderr)[-4000:]
+    assert r.returncode == 0 and "sanitize check ok" in r.stdout and "solver plans ok" in r.stdout and "buffers ok" in r.stdout and "lists ok" in r.stdout, (r.stdout + r.stderr)[-4000:]

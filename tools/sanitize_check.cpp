@@ -5,8 +5,9 @@
 // incremental (csrc/dpg_chol_sym.cpp), and the GPU solver's host planner (csrc/dpg_chol_plan.cpp:
 // its tables are followed by the kernels without bounds checks), driven through a small
 // end-to-end workload: scans -> clouds -> batched ICP + covariance -> factors -> Gauss-Newton ->
-// symbolic analysis -> solver plans -> DPG change detection over two passes; and the owning buffer
-// template of the GPU layer (csrc/dpg_buf.h) over host memory.  Any sanitizer report aborts
+// symbolic analysis -> solver plans -> DPG change detection over two passes; the owning buffer
+// template of the GPU layer (csrc/dpg_buf.h) over host memory; and the pose graphs' contribution
+// lists (dpg_contribution_lists) against a per-block construction.  Any sanitizer report aborts
 // (-fno-sanitize-recover).
 #include <math.h>
 #include <stdio.h>
@@ -204,6 +205,70 @@ static int buffer_checks() {
     return 0;
 }
 
+// dpg_contribution_lists against a per-block construction: block u's list is, factor by factor, the
+// entries whose block is u.  pairs are (lo, hi) in the caller's order; a Between's pair is looked up.
+static int lists_case(int64_t n, const std::vector<dpg_factor>& F, const std::vector<int32_t>& lo,
+                      const std::vector<int32_t>& hi) {
+    const int64_t nf = (int64_t)F.size(), P = (int64_t)lo.size(), nu = n + P;
+    std::vector<int32_t> pair((size_t)nf, -1);
+    size_t n_list = 0;
+    for (int64_t k = 0; k < nf; ++k) {
+        n_list += F[(size_t)k].kind == DPG_FACTOR_BETWEEN ? 3 : 1;
+        if (F[(size_t)k].kind != DPG_FACTOR_BETWEEN) continue;
+        for (int64_t p = 0; p < P; ++p)
+            if (lo[(size_t)p] == std::min(F[(size_t)k].i, F[(size_t)k].j) && hi[(size_t)p] == std::max(F[(size_t)k].i, F[(size_t)k].j))
+                pair[(size_t)k] = (int32_t)p;
+        REQUIRE(pair[(size_t)k] >= 0);
+    }
+    // exact sizes, so that a write past either array is the sanitizer's to report
+    std::vector<int32_t> cptr((size_t)nu + 1, -7), clist(n_list, -7), want;
+    dpg_contribution_lists(F.data(), nf, n, pair.data(), P, cptr.data(), clist.data());
+    REQUIRE(cptr[0] == 0);
+    for (int64_t u = 0; u < nu; ++u) {
+        REQUIRE((size_t)cptr[(size_t)u] == want.size());
+        for (int64_t k = 0; k < nf; ++k) {
+            const dpg_factor& f = F[(size_t)k];
+            if (u < n && f.i == u) want.push_back((int32_t)(k << 2 | 0));
+            if (f.kind != DPG_FACTOR_BETWEEN) continue;
+            if (u < n && f.j == u) want.push_back((int32_t)(k << 2 | 1));
+            if (u >= n && pair[(size_t)k] == u - n) want.push_back((int32_t)(k << 2 | (f.i < f.j ? 2 : 3)));
+        }
+    }
+    REQUIRE((size_t)cptr[(size_t)nu] == n_list && want == clist);
+    return 0;
+}
+
+static int lists_checks() {
+    const auto prior = [](int32_t i) { dpg_factor f; memset(&f, 0, sizeof(f)); f.kind = DPG_FACTOR_PRIOR; f.i = i; return f; };
+    const auto between = [](int32_t i, int32_t j) {
+        dpg_factor f;
+        memset(&f, 0, sizeof(f));
+        f.kind = DPG_FACTOR_BETWEEN;
+        f.i = i;
+        f.j = j;
+        return f;
+    };
+    REQUIRE(lists_case(1, {prior(0)}, {}, {}) == 0);                         // one node, one prior
+    REQUIRE(lists_case(2, {between(1, 0)}, {0}, {1}) == 0);                  // role 3
+    REQUIRE(lists_case(2, {between(0, 1), prior(0), between(1, 0), prior(1)}, {0}, {1}) == 0);   // both orientations
+    REQUIRE(lists_case(3, {}, {}, {}) == 0);                                 // no factors at all
+    std::vector<dpg_factor> F = {prior(0)};                                  // 12-node chain, a closure every 4th node
+    std::vector<int32_t> lo, hi;
+    for (int32_t v = 1; v < 12; ++v) {
+        F.push_back(between(v - 1, v));
+        lo.push_back(v - 1);
+        hi.push_back(v);
+        if (v % 4 == 0) {
+            F.push_back(between(v, v - 4));
+            lo.push_back(v - 4);
+            hi.push_back(v);
+        }
+    }
+    REQUIRE(lists_case(12, F, lo, hi) == 0);
+    printf("lists ok: 5 graphs\n");
+    return 0;
+}
+
 int main() {
     REQUIRE(buffer_checks() == 0);
     const int V = 24, NB = 720;
@@ -337,6 +402,8 @@ int main() {
     std::vector<float> mp(2 * (size_t)n + 2);
     REQUIRE(oracle_active_dynamic_points(D, V, est.data(), mp.data(), n, cnt) == n);
     oracle_dpg_destroy(D);
+    // the contribution lists of the batch and the incremental graph
+    REQUIRE(lists_checks() == 0);
     printf("sanitize check ok: %lld edges, %d GN iterations, %d supernodes, %lld map points\n", (long long)E,
            st.iterations, S.ns, (long long)n);
     return 0;
