@@ -1,8 +1,8 @@
 // dpg_chol_plan.cpp -- host planner of the GPU Cholesky (plain C++, no device call): from a symbolic
 // analysis (dpg_chol_sym.cpp), the solver options and the graph's pairs to a CholPlan
-// (dpg_chol_plan.h) -- the index tables the kernels of dpg_chol.hip follow WITHOUT bounds checks
-// and the launch parameters its driver reads.  One stage per function, in the order
-// dpg_chol_plan_build runs them.  -DDPG_PLAN_VERIFY checks the fast constructions against
+// (dpg_chol_plan.h) -- the index tables the kernels of dpg_chol*.hip follow WITHOUT bounds checks
+// and the launch parameters their driver reads.  One stage per function, in the order
+// dpg_chol_plan_build runs them; then the pick of the partial refactorization and the joint marginals' plan.  -DDPG_PLAN_VERIFY checks the fast constructions against
 // straightforward ones (tests/test_inc.py), -DDPG_PLAN_TIMING accumulates the stages' times
 // (tools/incsym_bench.cpp).
 #include <stdio.h>
@@ -464,7 +464,7 @@ void solve_orders(const dpg_chol_sym& S, const dpg_chol_opts& o, CholPlan& P) {
     P.bwd.resize((size_t)S.ns);
     for (int32_t s = S.ns - 1; s >= 0; --s)
         P.bwd[(size_t)cnt[(size_t)(nb - 1 - (int32_t)(hgt[(size_t)s] * 4.0))]++] = s;
-    // the sync words (layout: dpg_chol.hip, at the launch helpers): 2 tickets, 3 words per front,
+    // the sync words (layout: dpg_chol_dev.h): 2 tickets, 3 words per front,
     // one per large-front tile
     P.sync_bytes = ((size_t)(2 + 3 * S.ns + P.ftasks.size()) * sizeof(int32_t) + 15) & ~size_t(15);
     P.dblocks.clear();
@@ -596,6 +596,75 @@ int dpg_chol_plan_build(CholPlan& P, const dpg_chol_sym& S, const dpg_chol_opts&
     solve_orders(S, o, P);
     PLAN_T(7);
     return DPG_OK;
+}
+
+// ---- partial refactorization: the kept fronts and the runs that move them ----
+bool dpg_chol_plan_partial(PartialPick& K, const dpg_chol_sym& S, const dpg_chol_sym& O, const std::vector<int32_t>& cur_G,
+                           const std::vector<int32_t>& fac_G, const int32_t* dirty_nodes, int64_t n_dirty) {
+    const int32_t ns = S.ns;
+    K.keep.assign((size_t)ns, 1);
+    K.old.assign((size_t)ns, -1);
+    for (int64_t q = 0; q < n_dirty; ++q) {
+        const int32_t v = dirty_nodes[q];
+        if (v < 0 || v >= S.n) return false;
+        K.keep[(size_t)S.sn_of[(size_t)S.pos[(size_t)v]]] = 0;
+    }
+    K.kept = 0;
+    for (int32_t sn = 0; sn < ns; ++sn) {   // children before parents (a parent's first column is later)
+        if (K.keep[(size_t)sn]) {
+            const int32_t c0 = S.sn_c0[(size_t)sn], c1 = S.sn_c0[(size_t)sn + 1];
+            bool same = c1 <= O.n;
+            int32_t os = -1;
+            if (same) {
+                os = O.sn_of[(size_t)c0];
+                same = O.sn_c0[(size_t)os] == c0 && O.sn_c0[(size_t)os + 1] == c1 && fac_G[(size_t)os] == cur_G[(size_t)sn];
+            }
+            if (same) {
+                const int64_t r0 = S.sn_rows_ptr[(size_t)sn], r1 = S.sn_rows_ptr[(size_t)sn + 1];
+                const int64_t q0 = O.sn_rows_ptr[(size_t)os], q1 = O.sn_rows_ptr[(size_t)os + 1];
+                same = r1 - r0 == q1 - q0 && std::equal(S.sn_rows.begin() + r0, S.sn_rows.begin() + r1, O.sn_rows.begin() + q0);
+            }
+            if (same) {
+                const int64_t a0 = S.child_ptr[(size_t)sn], a1 = S.child_ptr[(size_t)sn + 1];
+                const int64_t b0 = O.child_ptr[(size_t)os], b1 = O.child_ptr[(size_t)os + 1];
+                same = a1 - a0 == b1 - b0;
+                for (int64_t t = 0; same && t < a1 - a0; ++t)
+                    same = S.sn_c0[(size_t)S.child_list[(size_t)(a0 + t)]] == O.sn_c0[(size_t)O.child_list[(size_t)(b0 + t)]];
+            }
+            if (same) {
+                K.old[(size_t)sn] = os;
+                ++K.kept;
+            } else {
+                K.keep[(size_t)sn] = 0;
+            }
+        }
+        if (!K.keep[(size_t)sn] && S.sn_parent[(size_t)sn] >= 0) K.keep[(size_t)S.sn_parent[(size_t)sn]] = 0;
+    }
+    if (K.kept == 0) return false;
+    // runs of kept fronts the layout moved (front s's pending updates sit at 3 sn_rows_ptr[s]: the plan's acc_off)
+    std::vector<int64_t>& runs = K.runs;
+    runs.clear();
+    K.moved = K.max_run = 0;
+    auto add_run = [&](int64_t src, int64_t dst, int64_t len, int64_t buf) {
+        if (src == dst || len == 0) return;
+        const size_t nr = runs.size();
+        if (nr >= 4 && runs[nr - 1] == buf && runs[nr - 4] + runs[nr - 2] == src && runs[nr - 3] + runs[nr - 2] == dst) {
+            runs[nr - 2] += len;
+        } else {
+            runs.insert(runs.end(), {src, dst, len, buf});
+        }
+        K.max_run = std::max(K.max_run, runs[runs.size() - 2]);
+        K.moved += len;
+    };
+    for (int32_t sn = 0; sn < ns; ++sn)
+        if (K.keep[(size_t)sn])
+            add_run(O.front_off[(size_t)K.old[(size_t)sn]], S.front_off[(size_t)sn],
+                    S.front_off[(size_t)sn + 1] - S.front_off[(size_t)sn], 0);
+    for (int32_t sn = 0; sn < ns; ++sn)
+        if (K.keep[(size_t)sn])
+            add_run(3 * O.sn_rows_ptr[(size_t)K.old[(size_t)sn]], 3 * S.sn_rows_ptr[(size_t)sn],
+                    3 * (S.sn_rows_ptr[(size_t)sn + 1] - S.sn_rows_ptr[(size_t)sn]), 1);
+    return runs.size() / 4 <= 65535;
 }
 
 // ---- joint marginals: root paths, W slices and per-block suffixes ----

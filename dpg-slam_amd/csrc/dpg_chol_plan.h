@@ -1,5 +1,5 @@
 // dpg_chol_plan.h -- what the Cholesky solver's host planner (dpg_chol_plan.cpp, plain C++) and its
-// kernels and driver (dpg_chol.hip) must agree on (private): the records the plan writes and the
+// kernels and driver (dpg_chol*.hip, dpg_chol_dev.h) must agree on (private): the records the plan writes and the
 // kernels follow, the tile / panel constants, the per-front cost model (also the symbolic
 // analysis's order choice, dpg_chol_sym.cpp), and CholPlan, everything one plan produces.
 #ifndef DPG_CHOL_PLAN_H
@@ -164,7 +164,7 @@ struct CholPlan {
     size_t lds_inv = 0;
     int64_t n_dblocks = 0;
     bool use_dinv = false;              // opts.solve_dinv: inverted diagonal blocks (measured slower)
-    size_t sync_bytes = 0;              // the sync words (layout: dpg_chol.hip, launch helpers)
+    size_t sync_bytes = 0;              // the sync words (layout: dpg_chol_dev.h)
     size_t lds_solve_max = 0;
     int32_t solve_stage = 0;   // R: LDS staging region of the solves, doubles (Stage)
     int32_t solve_maxseg = 0;  // backward: fronts with more row segments wait for the parent (<= kMaxSeg)
@@ -187,6 +187,26 @@ void dpg_chol_plan_prebucket(CholPlan& P, int64_t n, const int32_t* pos, const i
 // refactorization.  No device call; DPG_OK or a DPG_ERR_* code.
 int dpg_chol_plan_build(CholPlan& P, const dpg_chol_sym& S, const dpg_chol_opts& o, bool track, int64_t n,
                         const int32_t* pair_lo, const int32_t* pair_hi, int64_t n_pairs);
+
+// ---- partial refactorization: which fronts keep the last factorization's values (dpg_chol_solve_partial) ----
+struct PartialPick {
+    std::vector<uint8_t> keep;    // [ns] 1: the front keeps its values
+    std::vector<int32_t> old;     // [ns] a kept front's front in the old analysis, else -1
+    // the kept fronts (buf 0) and their pending forward-solve updates (buf 1) the new layout moved
+    std::vector<int64_t> runs;    // {src, dst, doubles, buf} per run, adjacent runs merged
+    int64_t kept = 0, moved = 0, max_run = 0;   // fronts kept, doubles moved, the longest run
+};
+// The pick for the new analysis S over the old one O (O's order a prefix of S's: the caller checks)
+// with their team sizes cur_G / fac_G and the nodes whose H blocks changed.  A front is kept when it has
+//   * the same columns (same first column, same count: positions are stable between reorders), the
+//     same rows, the same children (by first column, in order: the extend-add order) and the same
+//     team size (the arithmetic order of the factorization kernel) as a front of O;
+//   * no dirty node's column in it (its H blocks are then the same sums of the same factors at the
+//     same linearization point: the caller's contract);
+//   * no front below it that is not kept (its children's update matrices are unchanged).
+// False -- refactor everything -- on a dirty node out of range, nothing kept, or more than 65535 runs.
+bool dpg_chol_plan_partial(PartialPick& K, const dpg_chol_sym& S, const dpg_chol_sym& O, const std::vector<int32_t>& cur_G,
+                           const std::vector<int32_t>& fac_G, const int32_t* dirty_nodes, int64_t n_dirty);
 
 // ---- joint marginals: blocks of Sigma anywhere, from root paths of the factor (dpg_chol_joint) ----
 // W_q = L^-1 E_q (E_q: the three unit columns of node q) is nonzero only on the pivot rows of the

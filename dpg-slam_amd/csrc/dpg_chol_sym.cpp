@@ -2,7 +2,7 @@
 // supernodal multifrontal Cholesky (the CHOLESKY linear solver GTSAM runs inside
 // ISAM2 / GaussNewtonOptimizer).  Host code, run once per sparsity pattern
 // (dpg_gn_setup); the solver's host planner is dpg_chol_plan.cpp, the numeric factorization and
-// solves are in dpg_chol.hip.
+// solves are in dpg_chol*.hip.
 //
 //   1. fill-reducing order on the 3x3-block graph: nested dissection (BFS level separators) down
 //      to parts of <= 16 nodes, ordered by minimum degree (bitset elimination graphs, ties ->
@@ -966,7 +966,7 @@ static int sym_from_csr(int64_t n, const int32_t* perm, const int64_t* cp, const
         const int64_t r = S->sn_rows_ptr[(size_t)s + 1] - S->sn_rows_ptr[(size_t)s];
         const int64_t m3 = 3 * (k + r);
         // rounded up to an even count: every front starts 16-B aligned (the fused factorization's
-        // 16-B sc1 hand-offs, dpg_chol.hip front_rsrc)
+        // 16-B sc1 hand-offs, dpg_chol_dev.h front_rsrc)
         S->front_off[(size_t)s + 1] = S->front_off[(size_t)s] + ((m3 * m3 + 1) & ~(int64_t)1);
         maxm = std::max<int32_t>(maxm, (int32_t)(k + r));
         const double k3 = 3.0 * (double)k, r3 = 3.0 * (double)r;

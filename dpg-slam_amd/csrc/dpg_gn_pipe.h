@@ -27,7 +27,7 @@ struct dpg_gn_dev;
 
 // control block on the device
 struct dpg_gn_ctl {
-    int32_t active, reuse;          // the gate of the next iteration (gate_off in dpg_chol.hip)
+    int32_t active, reuse;          // the gate of the next iteration (gate_off in dpg_chol_dev.h)
     int32_t last_was_chord, have_factor, it;
     uint32_t loop;                  // the host's loop number (tags the reports of this loop)
     int32_t pad[2];
@@ -43,7 +43,7 @@ struct dpg_gn_slot {
 };
 
 // X_v <- X_v * Pose2(d) (Pose2 retraction); returns max |d|, NaN as +inf.  Shared by the
-// retraction kernel (dpg_gn.hip) and the backward solve that retracts as it goes (dpg_chol.hip).
+// retraction kernel (dpg_gn.hip) and the backward solve that retracts as it goes (dpg_chol_solve.hip).
 __device__ __forceinline__ double pose_retract(double* __restrict__ Xv, double d0, double d1, double d2) {
     const double c = cos(Xv[2]), s = sin(Xv[2]);
     const double cd = cos(d2), sd = sin(d2);

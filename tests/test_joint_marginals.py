@@ -1,5 +1,5 @@
 """Joint marginals and relative-pose covariances of ANY node pair (gtsam::Marginals::
-jointMarginalCovariance) from root paths of the Cholesky factor on the GPU (dpg_chol.hip
+jointMarginalCovariance) from root paths of the Cholesky factor on the GPU (dpg_chol_sel.hip
 chol_path_forward / chol_path_dot), against H^-1 on the CPU.
 
 Reference and tolerance are those of tests/test_marginals.py: per graph tol = max(1e-12, 100 x d),

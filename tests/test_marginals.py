@@ -1,5 +1,5 @@
 """Marginal pose covariances (gtsam::Marginals / ISAM2::marginalCovariance) by selected inversion
-of the Cholesky factor on the GPU (dpg_chol.hip chol_selinv_level), against H^-1 on the CPU.
+of the Cholesky factor on the GPU (dpg_chol_sel.hip chol_selinv_level), against H^-1 on the CPU.
 
 Reference: H = sum A^T Omega A from oracle.linearize, dense (sparse for config 3).  Every 3x3 block
 is compared by |S_gpu - S_ref|_F / |S_ref|_F.  The tolerance is not fixed: per graph it is

@@ -3,7 +3,8 @@
 // (dpg_oracle.c, dpg_change_oracle.cpp), the host half of the C ABI (csrc/dpg_host.c), the
 // synthetic workload generator (csrc/dpg_synth.c), the symbolic Cholesky analysis, full and
 // incremental (csrc/dpg_chol_sym.cpp), and the GPU solver's host planner (csrc/dpg_chol_plan.cpp:
-// its tables are followed by the kernels without bounds checks), driven through a small
+// its tables are followed by the kernels without bounds checks; its pick of the fronts a partial
+// refactorization keeps, and of the runs that move them, against the pick's contract), driven through a small
 // end-to-end workload: scans -> clouds -> batched ICP + covariance -> factors -> Gauss-Newton ->
 // symbolic analysis -> solver plans -> DPG change detection over two passes; the owning buffer
 // template of the GPU layer (csrc/dpg_buf.h) over host memory; and the pose graphs' contribution
@@ -77,8 +78,127 @@ static int plan_graph(int64_t n, const std::vector<int32_t>& lo, const std::vect
     return 0;
 }
 
+// One pick of the partial refactorization (dpg_chol_plan_partial) against its contract: (a) no kept
+// front holds a dirty node's column or lies above a front that is not kept; (b) a kept front's old
+// front has its columns, rows, children and team size; (c) the runs, applied as chol_copy_runs
+// applies them (all gathers into the scratch, then all scatters), leave every kept front's values
+// and pending rows at their new places and write nothing else.
+static int pick_holds(const dpg_chol::PartialPick& K, const dpg_chol_sym& S, const dpg_chol_sym& O,
+                      const std::vector<int32_t>& cur_G, const std::vector<int32_t>& fac_G, const std::vector<int32_t>& dirty) {
+    const size_t ns = (size_t)S.ns;
+    REQUIRE(K.keep.size() == ns && K.old.size() == ns && K.runs.size() % 4 == 0);
+    for (int32_t v : dirty) REQUIRE(!K.keep[(size_t)S.sn_of[(size_t)S.pos[(size_t)v]]]);
+    int64_t kept = 0;
+    for (size_t s = 0; s < ns; ++s) {
+        if (!K.keep[s]) {   // (by induction: nothing above a front that is not kept is kept)
+            REQUIRE(K.old[s] == -1 && (S.sn_parent[s] < 0 || !K.keep[(size_t)S.sn_parent[s]]));
+            continue;
+        }
+        ++kept;
+        REQUIRE(K.old[s] >= 0 && K.old[s] < O.ns);
+        const size_t o = (size_t)K.old[s];
+        REQUIRE(S.sn_c0[s] == O.sn_c0[o] && S.sn_c0[s + 1] == O.sn_c0[o + 1] && cur_G[s] == fac_G[o]);
+        const int64_t r0 = S.sn_rows_ptr[s], nr = S.sn_rows_ptr[s + 1] - r0, q0 = O.sn_rows_ptr[o];
+        REQUIRE(nr == O.sn_rows_ptr[o + 1] - q0 && std::equal(S.sn_rows.begin() + r0, S.sn_rows.begin() + r0 + nr, O.sn_rows.begin() + q0));
+        const int64_t a0 = S.child_ptr[s], nc = S.child_ptr[s + 1] - a0, b0 = O.child_ptr[o];
+        REQUIRE(nc == O.child_ptr[o + 1] - b0);
+        for (int64_t t = 0; t < nc; ++t)
+            REQUIRE(S.sn_c0[(size_t)S.child_list[(size_t)(a0 + t)]] == O.sn_c0[(size_t)O.child_list[(size_t)(b0 + t)]]);
+    }
+    REQUIRE(kept == K.kept && kept > 0);
+    // buffer 0: the fronts, buffer 1: the pending updates (front s at 3 sn_rows_ptr[s]); every old
+    // double encodes (front, offset), -1 outside the old layout
+    const auto enc = [](size_t front, int64_t off) { return (double)front * 4294967296.0 + (double)off; };
+    const int64_t old_end[2] = {O.front_off[(size_t)O.ns], 3 * O.sn_rows_ptr[(size_t)O.ns]};
+    const int64_t new_end[2] = {S.front_off[ns], 3 * S.sn_rows_ptr[ns]};
+    std::vector<double> buf[2], scratch((size_t)K.moved, -2.0);
+    std::vector<uint8_t> written[2];
+    for (int b = 0; b < 2; ++b) {
+        buf[b].assign((size_t)std::max(old_end[b], new_end[b]), -1.0);
+        written[b].assign(buf[b].size(), 0);
+    }
+    for (size_t o = 0; o < (size_t)O.ns; ++o) {
+        for (int64_t e = O.front_off[o]; e < O.front_off[o + 1]; ++e) buf[0][(size_t)e] = enc(o, e - O.front_off[o]);
+        for (int64_t e = 3 * O.sn_rows_ptr[o]; e < 3 * O.sn_rows_ptr[o + 1]; ++e) buf[1][(size_t)e] = enc(o, e - 3 * O.sn_rows_ptr[o]);
+    }
+    int64_t off = 0, max_run = 0;
+    for (size_t r = 0; r < K.runs.size(); r += 4) {   // gather {src, scratch}
+        const int64_t src = K.runs[r], len = K.runs[r + 2], b = K.runs[r + 3];
+        REQUIRE((b == 0 || b == 1) && len > 0 && src >= 0 && src + len <= old_end[b] && off + len <= K.moved);
+        std::copy(buf[b].begin() + src, buf[b].begin() + src + len, scratch.begin() + off);
+        off += len;
+        max_run = std::max(max_run, len);
+    }
+    REQUIRE(off == K.moved && max_run == K.max_run);
+    off = 0;
+    for (size_t r = 0; r < K.runs.size(); r += 4) {   // scatter {scratch, dst}
+        const int64_t dst = K.runs[r + 1], len = K.runs[r + 2], b = K.runs[r + 3];
+        REQUIRE(dst >= 0 && dst + len <= new_end[b]);
+        std::copy(scratch.begin() + off, scratch.begin() + off + len, buf[b].begin() + dst);
+        std::fill(written[b].begin() + dst, written[b].begin() + dst + len, 1);
+        off += len;
+    }
+    for (size_t s = 0; s < ns; ++s) {
+        if (!K.keep[s]) continue;
+        const int64_t lo[2] = {S.front_off[s], 3 * S.sn_rows_ptr[s]}, hi[2] = {S.front_off[s + 1], 3 * S.sn_rows_ptr[s + 1]};
+        for (int b = 0; b < 2; ++b)
+            for (int64_t e = lo[b]; e < hi[b]; ++e) {
+                REQUIRE(buf[b][(size_t)e] == enc((size_t)K.old[s], e - lo[b]));
+                written[b][(size_t)e] = 0;
+            }
+    }
+    for (int b = 0; b < 2; ++b) REQUIRE(std::find(written[b].begin(), written[b].end(), 1) == written[b].end());
+    return 0;
+}
+
+// The pick for a graph analysed before and after node n with edges to `nbr` is appended, through the
+// incremental symbolic analysis as the incremental graph runs it (the old order is a prefix of the
+// new one), then its exceptions: a dirty node out of range, every node dirty, one leaf front dirty.
+static int partial_graph(int64_t n, std::vector<int32_t> lo, std::vector<int32_t> hi, const std::vector<int32_t>& nbr,
+                         int64_t* kept, int64_t* moved) {
+    using dpg_chol::dpg_chol_plan_partial;
+    const dpg_chol_opts o{64, 0.3};
+    dpg_chol_incsym I;
+    dpg_chol_sym O, S;
+    dpg_chol::CholPlan P;
+    REQUIRE(dpg_incsym_reset(&I, n, lo.data(), hi.data(), (int64_t)lo.size(), &o) == 0 && dpg_incsym_derive(&I, &o, &O) == 0);
+    REQUIRE(dpg_chol_plan_build(P, O, o, true, n, lo.data(), hi.data(), (int64_t)lo.size()) == DPG_OK);
+    const std::vector<int32_t> fac_G = P.cur_G;
+    dpg_incsym_append(&I, 1);
+    std::vector<int32_t> dirty(1, (int32_t)n);
+    for (int32_t u : nbr) {
+        dpg_incsym_add_edge(&I, u, (int32_t)n);
+        lo.push_back(u);
+        hi.push_back((int32_t)n);
+        dirty.push_back(u);
+    }
+    REQUIRE(dpg_incsym_derive(&I, &o, &S) == 0);
+    REQUIRE(dpg_chol_plan_build(P, S, o, true, n + 1, lo.data(), hi.data(), (int64_t)lo.size()) == DPG_OK);
+    REQUIRE(O.n == n && S.n == n + 1 && std::equal(O.perm.begin(), O.perm.end(), S.perm.begin()));
+    REQUIRE((int64_t)fac_G.size() == O.ns && (int64_t)P.cur_G.size() == S.ns);
+    dpg_chol::PartialPick K;
+    REQUIRE(dpg_chol_plan_partial(K, S, O, P.cur_G, fac_G, dirty.data(), (int64_t)dirty.size()));
+    REQUIRE(pick_holds(K, S, O, P.cur_G, fac_G, dirty) == 0 && K.kept < S.ns);
+    *kept = K.kept;
+    *moved = K.moved;
+    const int32_t out[4] = {nbr[0], (int32_t)(n + 1), nbr[0], -1};
+    REQUIRE(!dpg_chol_plan_partial(K, S, O, P.cur_G, fac_G, out, 2) && !dpg_chol_plan_partial(K, S, O, P.cur_G, fac_G, out + 2, 2));
+    std::vector<int32_t> all((size_t)n + 1);
+    for (size_t v = 0; v < all.size(); ++v) all[v] = (int32_t)v;
+    REQUIRE(!dpg_chol_plan_partial(K, S, O, P.cur_G, fac_G, all.data(), (int64_t)all.size()));
+    int32_t leaf = -1;   // a childless front of old columns, not the new node's
+    for (int32_t s = 0; s < S.ns && leaf < 0; ++s)
+        if (S.child_ptr[(size_t)s] == S.child_ptr[(size_t)s + 1] && S.sn_c0[(size_t)s + 1] <= O.n && S.sn_parent[(size_t)s] >= 0) leaf = s;
+    REQUIRE(leaf >= 0);
+    const std::vector<int32_t> one(1, S.perm[(size_t)S.sn_c0[(size_t)leaf]]);
+    REQUIRE(dpg_chol_plan_partial(K, S, O, P.cur_G, fac_G, one.data(), 1) && K.kept > 0 && !K.keep[(size_t)leaf]);
+    REQUIRE(pick_holds(K, S, O, P.cur_G, fac_G, one) == 0);
+    return 0;
+}
+
 static int plan_checks() {
     std::vector<int32_t> lo, hi;
+    int64_t kept[2] = {0, 0}, moved[2] = {0, 0};
     const int M = 30;   // M x M 4-neighbour mesh: separator fronts past the in-LDS limit (teams)
     for (int r = 0; r < M; ++r)
         for (int c = 0; c < M; ++c) {
@@ -86,6 +206,7 @@ static int plan_checks() {
             if (r + 1 < M) { lo.push_back(r * M + c); hi.push_back((r + 1) * M + c); }
         }
     REQUIRE(plan_graph(M * M, lo, hi, true) == 0);
+    REQUIRE(partial_graph(M * M, lo, hi, {M * M - 1, M * M - 2, M - 1}, &kept[0], &moved[0]) == 0);
     // a 700-node chain with up to three random loop closures per node (tests/test_inc.py's graph)
     lo.clear();
     hi.clear();
@@ -101,7 +222,11 @@ static int plan_checks() {
         for (int k = 0; k < ne; ++k) { lo.push_back(e[k]); hi.push_back(v); }
     }
     REQUIRE(plan_graph(700, lo, hi, false) == 0);
+    REQUIRE(partial_graph(700, lo, hi, {699, 350}, &kept[1], &moved[1]) == 0);
     printf("solver plans ok: %d x %d mesh, 700-node loop graph\n", M, M);
+    REQUIRE(moved[0] + moved[1] > 0);   // (the runs were exercised)
+    printf("partial pick ok: one node appended, %lld and %lld fronts kept, %lld and %lld doubles moved\n", (long long)kept[0],
+           (long long)kept[1], (long long)moved[0], (long long)moved[1]);
     return 0;
 }
 
