@@ -60,10 +60,16 @@ int dpg_chol_order_nd(int64_t n, const int32_t* pair_lo, const int32_t* pair_hi,
                       std::vector<int32_t>& perm, std::vector<std::vector<int32_t>>& pat);
 // the same with the separator rule of the multi-start search (starts = 0: round 2's rule; bal:
 // both sides >= 1 / bal of the part; score 0 |S|, 1 |S| N / min side, 2 |S| sqrt(N / min side);
-// cover: the chosen cut's separator as a minimum vertex cover of its crossing edges)
+// cover: the chosen cut's separator as a minimum vertex cover of its crossing edges; refine > 0,
+// with starts > 0: every split's separator refined by at most that many passes of node-based
+// Fiduccia-Mattheyses moves under the same balance rule and score)
 int dpg_chol_order_nd_sep(int64_t n, const int32_t* pair_lo, const int32_t* pair_hi, int64_t n_pairs, int32_t leaf,
                           int32_t starts, int32_t bal, int32_t score, bool cover, std::vector<int32_t>& perm,
-                          std::vector<std::vector<int32_t>>& pat, bool par = false);
+                          std::vector<std::vector<int32_t>>& pat, bool par = false, int32_t refine = 0);
+// the refinement alone, on a separator of the whole graph: side[v] = 0 (A), 1 (B) or 2 (separator),
+// refined in place
+int dpg_chol_nd_refine(int64_t n, const int32_t* pair_lo, const int32_t* pair_hi, int64_t n_pairs, int32_t bal,
+                       int32_t score, int32_t refine, std::vector<int32_t>& side);
 int dpg_chol_sym_from_patterns(int64_t n, const std::vector<int32_t>& perm, const std::vector<std::vector<int32_t>>& pat,
                                const dpg_chol_opts* opts, dpg_chol_sym* S);
 // the fused factorization's critical-path estimate (us) of an analysis: the per-front model the

@@ -122,6 +122,7 @@ struct NdParams {
     int32_t starts = 0, bal = 5, score = 0;
     bool cover = false;   // the chosen cut's separator as a minimum vertex cover of its crossing edges
     bool par = false;     // the two halves of a large part ordered on two threads (same order)
+    int32_t refine = 0;   // passes of the vertex-separator refinement after each split (0: none)
 };
 // Per-vertex scratch shared by the parallel halves of a split (the parts are disjoint: a part only
 // writes its own vertices; it reads a neighbour's stamp, which another part may be writing, only
@@ -344,6 +345,162 @@ NdCut nd_best_cut(const NdState& st, const std::vector<int32_t>& sub, int32_t id
     return best;
 }
 
+// Vertex-separator refinement (round 7; NdParams.refine passes at most): the level-structure cut's
+// separator sits on a level boundary, and a smaller one is often a few vertices away.  Node-based
+// Fiduccia-Mattheyses moves, as in METIS's node refinement: a separator vertex v moves to one side
+// and its neighbours on the other side enter the separator (gain 1 - |N(v) in the other side|).  A
+// pass hill-climbs -- the unlocked separator vertex of largest gain, ties -> the move towards the
+// smaller side, then the lower position in `sub`; a moved vertex is locked for the pass -- through
+// at most `limit` moves in a row that do not improve on the pass's best state, then rolls back to
+// that state; passes repeat while they improve.  A move must leave the side it takes vertices from
+// at least N / bal (the cut's own balance rule), and states are compared as the cuts are: by the
+// cut's score (score 2: |S| sqrt(N / min side)), ties -> the smaller imbalance -- a smaller but
+// lopsided separator does not win.
+// The part's vertices are addressed by their position in `sub` (kept in the shared aux array, which
+// is -1 again on return): all other state is local, so the halves of a part refine on two threads
+// as they split.  Built with DPG_ND_VERIFY the result is checked: no edge joins A and B.
+// Parts of fewer than kNdRefineMin nodes keep their cut (the multi-start search's own threshold):
+// the critical path's large separators are above it, and refining below it lengthens the host's
+// ordering for no shorter path (config 4: estimate 661 us refining every part, 647 us so).
+constexpr int64_t kNdRefineMin = 256;
+void nd_refine(NdState& st, const std::vector<int32_t>& sub, std::vector<int32_t>& A, std::vector<int32_t>& B,
+               std::vector<int32_t>& S) {
+    const int64_t N = (int64_t)sub.size();
+    if (A.empty() || B.empty() || S.empty()) return;
+    int32_t* pos = st.sh->aux.data();
+    for (int64_t i = 0; i < N; ++i) pos[sub[(size_t)i]] = (int32_t)i;
+    enum : uint8_t { kA = 0, kB = 1, kS = 2 };
+    std::vector<uint8_t> side((size_t)N, kS);
+    for (int32_t v : A) side[(size_t)pos[v]] = kA;
+    for (int32_t v : B) side[(size_t)pos[v]] = kB;
+    int64_t sz[3] = {(int64_t)A.size(), (int64_t)B.size(), (int64_t)S.size()};
+    const int64_t bal = st.prm.bal;
+    auto score_of = [&](int64_t s, int64_t a, int64_t b) {
+        const double mn = (double)std::min(a, b);
+        if (mn <= 0.0) return HUGE_VAL;
+        return st.prm.score == 2 ? (double)s * sqrt((double)N / mn)
+               : st.prm.score == 1 ? (double)s * (double)N / mn : (double)s;
+    };
+    // neighbours in A and in B, kept for the separator's vertices only (counted when a vertex enters
+    // the separator, updated as its neighbours change sides): a pass costs what it touches
+    std::vector<int32_t> cnt[2];
+    cnt[0].resize((size_t)N);
+    cnt[1].resize((size_t)N);
+    std::vector<char> locked((size_t)N, 0), mark((size_t)N, 0);
+    std::vector<int32_t> sep, sep0;                  // the separator's positions (any order); at the pass's start
+    std::vector<std::pair<int32_t, uint8_t>> log;    // (position, the side it left), in move order
+    auto count = [&](int32_t i) {
+        int32_t c[3] = {0, 0, 0};
+        const int32_t v = sub[(size_t)i];
+        for (const int32_t *p = nbr_begin(st, v), *e = nbr_end(st, v); p != e; ++p) c[side[(size_t)pos[*p]]]++;
+        cnt[0][(size_t)i] = c[kA];
+        cnt[1][(size_t)i] = c[kB];
+    };
+    auto set_side = [&](int32_t i, uint8_t to) {
+        const uint8_t from = side[(size_t)i];
+        log.emplace_back(i, from);
+        side[(size_t)i] = to;
+        sz[from]--;
+        sz[to]++;
+        const int32_t v = sub[(size_t)i];
+        for (const int32_t *p = nbr_begin(st, v), *e = nbr_end(st, v); p != e; ++p) {
+            const int32_t j = pos[*p];
+            if (side[(size_t)j] != kS) continue;
+            if (from != kS) cnt[from][(size_t)j]--;
+            if (to != kS) cnt[to][(size_t)j]++;
+        }
+        if (to == kS) count(i);
+    };
+    for (int32_t v : S) sep.push_back(pos[v]);
+    const int32_t limit = (int32_t)std::min<int64_t>(100, std::max<int64_t>(15, N / 100));
+    bool changed = false;
+    for (int32_t pass = 0; pass < st.prm.refine; ++pass) {
+        for (int32_t i : sep) count(i);
+        sep0 = sep;
+        log.clear();
+        double best_sc = score_of(sz[kS], sz[kA], sz[kB]);
+        int64_t best_imb = sz[kA] > sz[kB] ? sz[kA] - sz[kB] : sz[kB] - sz[kA];
+        size_t best_len = 0;
+        for (int32_t bad = 0; bad < limit;) {
+            int32_t bi = -1, bto = 0, bgain = 0;
+            size_t bk = 0;
+            for (size_t k = 0; k < sep.size(); ++k) {
+                const int32_t i = sep[k];
+                if (locked[(size_t)i]) continue;
+                for (int32_t to = 0; to < 2; ++to) {
+                    const int32_t other = 1 - to, pulled = cnt[other][(size_t)i];
+                    if (pulled > 0 && bal * (sz[other] - pulled) < N) continue;
+                    const int32_t gain = 1 - pulled;
+                    bool better = bi < 0 || gain > bgain;
+                    if (!better && gain == bgain) {
+                        const bool small = sz[to] < sz[other], bsmall = sz[bto] < sz[1 - bto];
+                        better = small != bsmall ? small : i < bi;
+                    }
+                    if (better) { bi = i; bto = to; bgain = gain; bk = k; }
+                }
+            }
+            if (bi < 0) break;
+            sep[bk] = sep.back();
+            sep.pop_back();
+            locked[(size_t)bi] = 1;
+            set_side(bi, (uint8_t)bto);
+            const int32_t v = sub[(size_t)bi];
+            for (const int32_t *p = nbr_begin(st, v), *e = nbr_end(st, v); p != e; ++p) {
+                const int32_t j = pos[*p];
+                if (side[(size_t)j] == 1 - bto) { set_side(j, kS); sep.push_back(j); }
+            }
+            const double sc = score_of(sz[kS], sz[kA], sz[kB]);
+            const int64_t imb = sz[kA] > sz[kB] ? sz[kA] - sz[kB] : sz[kB] - sz[kA];
+            if (sc < best_sc || (sc == best_sc && imb < best_imb)) {
+                best_sc = sc;
+                best_imb = imb;
+                best_len = log.size();
+                bad = 0;
+            } else {
+                ++bad;
+            }
+        }
+        for (size_t k = log.size(); k-- > best_len;) {   // back to the best state (the next pass recounts)
+            const int32_t i = log[k].first;
+            sz[side[(size_t)i]]--;
+            side[(size_t)i] = log[k].second;
+            sz[side[(size_t)i]]++;
+        }
+        // the separator now: among what it held at the pass's start and what the pass moved
+        sep.clear();
+        auto take = [&](int32_t i) {
+            locked[(size_t)i] = 0;
+            if (side[(size_t)i] == kS && !mark[(size_t)i]) { mark[(size_t)i] = 1; sep.push_back(i); }
+        };
+        for (int32_t i : sep0) take(i);
+        for (auto& m : log) take(m.first);
+        for (int32_t i : sep) mark[(size_t)i] = 0;
+        if (best_len == 0) break;
+        changed = true;
+    }
+    if (changed) {
+        A.clear();
+        B.clear();
+        S.clear();
+        for (int64_t i = 0; i < N; ++i) (side[(size_t)i] == kA ? A : side[(size_t)i] == kB ? B : S).push_back(sub[(size_t)i]);
+    }
+#ifdef DPG_ND_VERIFY
+    for (int64_t i = 0; i < N; ++i) {
+        const int32_t v = sub[(size_t)i];
+        for (const int32_t *p = nbr_begin(st, v), *e = nbr_end(st, v); p != e; ++p)
+            if (side[(size_t)i] != kS && side[(size_t)pos[*p]] != kS && side[(size_t)pos[*p]] != side[(size_t)i]) {
+                fprintf(stderr, "nd_refine: edge %d - %d joins the two sides\n", v, *p);
+                abort();
+            }
+    }
+    if ((int64_t)(A.size() + B.size() + S.size()) != N || A.empty() || B.empty()) {
+        fprintf(stderr, "nd_refine: sides %zu + %zu + %zu of %lld\n", A.size(), B.size(), S.size(), (long long)N);
+        abort();
+    }
+#endif
+    for (int32_t v : sub) pos[v] = -1;
+}
+
 // the separator search with several level structures (NdParams, starts > 0); src is the part's
 // pseudo-peripheral node, `id` its stamp; have_h > 0: the shared level array and queue hold the
 // level structure from src already (of height have_h: the pseudo-peripheral search's last BFS).
@@ -495,6 +652,7 @@ void nd_split_multi(NdState& st, std::vector<int32_t>& sub, int32_t id, int32_t 
             }
         }
     }
+    if (st.prm.refine > 0 && N >= kNdRefineMin) nd_refine(st, sub, A, B, S);
     nd_halves(st, A, B, S);
 }
 
@@ -637,7 +795,7 @@ int dpg_chol_order_nd(int64_t n, const int32_t* pair_lo, const int32_t* pair_hi,
 
 int dpg_chol_order_nd_sep(int64_t n, const int32_t* pair_lo, const int32_t* pair_hi, int64_t n_pairs, int32_t leaf,
                           int32_t starts, int32_t bal, int32_t score, bool cover, std::vector<int32_t>& perm,
-                          std::vector<std::vector<int32_t>>& pat, bool par) {
+                          std::vector<std::vector<int32_t>>& pat, bool par, int32_t refine) {
     if (n <= 0) return -1;
     std::vector<int64_t> aptr((size_t)n + 1, 0);
     for (int64_t p = 0; p < n_pairs; ++p) { aptr[(size_t)pair_lo[p] + 1]++; aptr[(size_t)pair_hi[p] + 1]++; }
@@ -660,6 +818,7 @@ int dpg_chol_order_nd_sep(int64_t n, const int32_t* pair_lo, const int32_t* pair
     st.prm.score = score;
     st.prm.cover = cover && starts > 0;
     st.prm.par = par;
+    st.prm.refine = starts > 0 ? std::max<int32_t>(refine, 0) : 0;
     NdShared sh;
     sh.aux.assign((size_t)n, -1);
     sh.stamp.assign((size_t)n, 0);
@@ -675,6 +834,48 @@ int dpg_chol_order_nd_sep(int64_t n, const int32_t* pair_lo, const int32_t* pair
     nd_rec(st, all);
     if ((int64_t)perm.size() != n) return -1;
     patterns_of_order(n, aptr, adj, perm, pat);
+    return 0;
+}
+
+int dpg_chol_nd_refine(int64_t n, const int32_t* pair_lo, const int32_t* pair_hi, int64_t n_pairs, int32_t bal,
+                       int32_t score, int32_t refine, std::vector<int32_t>& side) {
+    if (n <= 0 || (int64_t)side.size() != n) return -1;
+    std::vector<int64_t> aptr((size_t)n + 1, 0);
+    for (int64_t p = 0; p < n_pairs; ++p) { aptr[(size_t)pair_lo[p] + 1]++; aptr[(size_t)pair_hi[p] + 1]++; }
+    for (int64_t v = 0; v < n; ++v) aptr[(size_t)v + 1] += aptr[(size_t)v];
+    std::vector<int32_t> adj((size_t)aptr[(size_t)n]);
+    {
+        std::vector<int64_t> cur(aptr.begin(), aptr.end() - 1);
+        for (int64_t p = 0; p < n_pairs; ++p) {
+            adj[(size_t)cur[(size_t)pair_lo[p]]++] = pair_hi[p];
+            adj[(size_t)cur[(size_t)pair_hi[p]]++] = pair_lo[p];
+        }
+    }
+    NdState st;
+    st.n = n;
+    st.aptr = aptr.data();
+    st.adj = adj.data();
+    st.leaf = 16;
+    st.prm.bal = std::max<int32_t>(bal, 2);
+    st.prm.score = score;
+    st.prm.refine = std::max<int32_t>(refine, 0);
+    NdShared sh;
+    sh.aux.assign((size_t)n, -1);
+    sh.stamp.assign((size_t)n, 1);   // the whole graph is the part (id 1)
+    sh.fptr.assign((size_t)n, 0);
+    sh.fcnt.assign((size_t)n, 0);
+    st.sh = &sh;
+    std::vector<int32_t> sub((size_t)n), A, B, S, fadj;
+    for (int64_t v = 0; v < n; ++v) {
+        sub[(size_t)v] = (int32_t)v;
+        if (side[(size_t)v] < 0 || side[(size_t)v] > 2) return -1;
+        (side[(size_t)v] == 0 ? A : side[(size_t)v] == 1 ? B : S).push_back((int32_t)v);
+    }
+    nd_filter(st, sub, 1, fadj);
+    if (st.prm.refine > 0) nd_refine(st, sub, A, B, S);
+    for (int32_t v : A) side[(size_t)v] = 0;
+    for (int32_t v : B) side[(size_t)v] = 1;
+    for (int32_t v : S) side[(size_t)v] = 2;
     return 0;
 }
 
@@ -731,9 +932,15 @@ double dpg_chol_critical_path_us(const dpg_chol_sym& S) {
 // estimate is shortest is kept.  Config 4 (tools/nd_ab2_job.sh, profiles/r03/v15_nd_cover_ab.txt):
 // factor + solve 0.860 -> 0.716 ms, chord-step solves 0.251 -> 0.230 ms; config 3 keeps round 2's
 // order (0.282 ms; the others 0.29-0.34).
-// The incremental graph (dpg_incsym_order) reorders every 64 nodes with the same pick, on a worker
-// thread (dpg_inc.hip).
+// Round 7 adds a third candidate: the 8-start search scored by |S|, cover separators refined by
+// kNdRefinePasses passes of nd_refine.  Config 4 (profiles/r07/nd_refine.md): estimate 711 -> 647 us,
+// factorization 547 -> 501 us per refactor in the bench step, step 8.08 -> 7.86 ms; config 3's
+// estimate 299 -> 271 us.  Refining the {8, 4, 2} rule itself lengthens the path (804 us) and is
+// not a candidate.
+// The incremental graph (dpg_incsym_order) reorders every 64 nodes with the first two candidates,
+// unrefined, on a worker thread (dpg_inc.hip).
 // opts->order DPG_ORDER_ND (2) keeps round 2's single order, DPG_ORDER_MD (1) plain minimum degree.
+constexpr int32_t kNdRefinePasses = 4;
 int dpg_chol_symbolic(int64_t n, const int32_t* pair_lo, const int32_t* pair_hi, int64_t n_pairs,
                       const dpg_chol_opts* opts, dpg_chol_sym* S) {
     std::vector<int32_t> perm;
@@ -743,31 +950,38 @@ int dpg_chol_symbolic(int64_t n, const int32_t* pair_lo, const int32_t* pair_hi,
         if (dpg_chol_order(n, pair_lo, pair_hi, n_pairs, perm, pat, order == 1)) return -1;
         return dpg_chol_sym_from_patterns(n, perm, pat, opts, S);
     }
-    struct Cand { int32_t starts, bal, score; };
-    static const Cand cands[] = {{0, 5, 0}, {8, 4, 2}};
+    struct Cand { int32_t starts, bal, score, refine; };
+    static const Cand cands[] = {{0, 5, 0, 0}, {8, 4, 2, 0}, {8, 4, 0, kNdRefinePasses}};
+    constexpr int kCands = (int)(sizeof(cands) / sizeof(cands[0]));
     struct Res {
         int rc = 0;
         double cp = 0.0;
         dpg_chol_sym T;
     };
-    // both candidates at once (thread-local scratch); the first kept unless the second is shorter
+    // the candidates at once (thread-local scratch); an earlier one kept unless a later is shorter
     auto run = [&](int k) {
         Res r;
         std::vector<int32_t> pm;
         std::vector<std::vector<int32_t>> pt;
         if (dpg_chol_order_nd_sep(n, pair_lo, pair_hi, n_pairs, 16, cands[k].starts, cands[k].bal, cands[k].score, true,
-                                  pm, pt, true) ||
+                                  pm, pt, true, cands[k].refine) ||
             dpg_chol_sym_from_patterns(n, pm, pt, opts, &r.T))
             r.rc = -1;
         else
             r.cp = dpg_chol_critical_path_us(r.T);
         return r;
     };
-    std::future<Res> second = std::async(std::launch::async, run, 1);
-    Res r0 = run(0);
-    Res r1 = second.get();
-    if (r0.rc || r1.rc) return -1;
-    *S = std::move(r1.cp < r0.cp ? r1.T : r0.T);
+    std::future<Res> later[kCands - 1];
+    for (int k = 1; k < kCands; ++k) later[k - 1] = std::async(std::launch::async, run, k);
+    Res res[kCands];
+    res[0] = run(0);
+    for (int k = 1; k < kCands; ++k) res[k] = later[k - 1].get();
+    int b = 0;
+    for (int k = 0; k < kCands; ++k) {
+        if (res[k].rc) return -1;
+        if (res[k].cp < res[b].cp) b = k;
+    }
+    *S = std::move(res[b].T);
     return 0;
 }
 

@@ -38,6 +38,37 @@ static void report(const char* name, double ms, const dpg_chol_sym& S) {
            name, ms, (long long)nnz, S.flops * 1e-6, S.ns, S.n_levels, S.max_front, crit, work);
 }
 
+// the fronts on the critical path (dpg_chol_critical_path_us's longest leaf-to-root path), root
+// first: pivot columns k and rows below r (blocks), panels of kFNB scalar columns (0: a small front,
+// factored whole in LDS), children, the model's estimate
+static void path_fronts(const dpg_chol_sym& S) {
+    std::vector<double> cp((size_t)S.ns, 0.0), est((size_t)S.ns, 0.0);
+    int32_t far = -1;
+    for (int32_t s = S.ns - 1; s >= 0; --s) {
+        const int32_t k = S.sn_c0[(size_t)s + 1] - S.sn_c0[(size_t)s];
+        const int32_t r = (int32_t)(S.sn_rows_ptr[(size_t)s + 1] - S.sn_rows_ptr[(size_t)s]);
+        const int32_t p = S.sn_parent[(size_t)s];
+        est[(size_t)s] = dpg_chol::front_est_us(3 * (k + r), 3 * k, (int32_t)(S.child_ptr[(size_t)s + 1] - S.child_ptr[(size_t)s]));
+        cp[(size_t)s] = est[(size_t)s] + (p >= 0 ? cp[(size_t)p] : 0.0);
+        if (far < 0 || cp[(size_t)s] >= cp[(size_t)far]) far = s;   // ties -> the lowest front
+    }
+    std::vector<int32_t> path;
+    for (int32_t s = far; s >= 0; s = S.sn_parent[(size_t)s]) path.push_back(s);
+    int32_t panels = 0, cols = 0;
+    printf("critical path: %zu fronts, ~%.0f us\n   front     k     r  panels  children  est us\n", path.size(), cp[(size_t)far]);
+    for (size_t i = path.size(); i-- > 0;) {
+        const int32_t s = path[i];
+        const int32_t k = S.sn_c0[(size_t)s + 1] - S.sn_c0[(size_t)s];
+        const int32_t r = (int32_t)(S.sn_rows_ptr[(size_t)s + 1] - S.sn_rows_ptr[(size_t)s]);
+        const int32_t nch = (int32_t)(S.child_ptr[(size_t)s + 1] - S.child_ptr[(size_t)s]);
+        const int32_t np = dpg_chol::front_is_small(3 * (k + r), nch) ? 0 : (3 * k + dpg_chol::kFNB - 1) / dpg_chol::kFNB;
+        panels += np;
+        cols += k;
+        printf("  %6d  %4d  %4d  %6d  %8d  %6.1f\n", s, k, r, np, nch, est[(size_t)s]);
+    }
+    printf("  path total: %d pivot columns, %d panels\n", cols, panels);
+}
+
 int main(int argc, char** argv) {
     if (argc < 2) return 2;
     FILE* f = fopen(argv[1], "rb");
@@ -62,22 +93,31 @@ int main(int argc, char** argv) {
     }
     for (int k = 0; k < 4; ++k) {   // the batch analysis' candidates (dpg_chol_symbolic picks the shortest path)
         static const int prm[4][3] = {{0, 5, 0}, {2, 4, 2}, {8, 4, 2}, {4, 5, 1}};
-        std::vector<int32_t> perm;
-        std::vector<std::vector<int32_t>> pat;
-        const double t = now_ms();
-        if (dpg_chol_order_nd_sep(n, lo.data(), hi.data(), P, 16, prm[k][0], prm[k][1], prm[k][2], k > 0, perm, pat)) return 3;
-        const double ms = now_ms() - t;
-        dpg_chol_sym S;
-        if (dpg_chol_sym_from_patterns(n, perm, pat, &o, &S)) return 4;
-        char name[32];
-        snprintf(name, sizeof(name), "sep/%d", k);
-        report(name, ms, S);
+        // each multi-start rule plain and with its separators refined (1, 4, 8 passes)
+        for (int refine : {0, 1, 4, 8}) {
+            if (refine > 0 && prm[k][0] == 0) continue;
+            std::vector<int32_t> perm;
+            std::vector<std::vector<int32_t>> pat;
+            const double t = now_ms();
+            if (dpg_chol_order_nd_sep(n, lo.data(), hi.data(), P, 16, prm[k][0], prm[k][1], prm[k][2], k > 0, perm, pat, false,
+                                      refine))
+                return 3;
+            const double ms = now_ms() - t;
+            dpg_chol_sym S;
+            if (dpg_chol_sym_from_patterns(n, perm, pat, &o, &S)) return 4;
+            char name[32];
+            if (refine > 0) snprintf(name, sizeof(name), "sep/%d+r%d", k, refine);
+            else snprintf(name, sizeof(name), "sep/%d", k);
+            report(name, ms, S);
+            if (argc > 2) path_fronts(S);   // any second argument: every candidate's path
+        }
     }
     {
         const double t = now_ms();
         dpg_chol_sym S;
         if (dpg_chol_symbolic(n, lo.data(), hi.data(), P, &o, &S)) return 5;
         report("batch-pick", now_ms() - t, S);
+        path_fronts(S);
     }
     for (int leaf : {32, 64, 128, 256, 512}) {
         std::vector<int32_t> perm;
