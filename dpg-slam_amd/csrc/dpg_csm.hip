@@ -28,7 +28,7 @@
 #include <math.h>
 #include <string.h>
 
-#include "dpg_ctx.h"
+#include "dpg_raster.h"   // cell_key
 
 namespace {
 
@@ -50,15 +50,6 @@ struct CsmArgs {
     double res_m;                 // (double)resolution
     int32_t H, hx, hy, ha, R, n_passes;
 };
-
-// round((double)v / res) when the point counts (finite, |v / res| < 2^29)
-__device__ __forceinline__ bool cell_key(float x, float y, double res, int& kx, int& ky) {
-    const double dx = (double)x / res, dy = (double)y / res;
-    if (!(fabs(dx) < 536870912.0) || !(fabs(dy) < 536870912.0)) return false;
-    kx = (int)round(dx);
-    ky = (int)round(dy);
-    return true;
-}
 
 __global__ __launch_bounds__(kT) void csm_kernel(CsmArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];

@@ -3,7 +3,8 @@
 // boundary is split by subsystem over dpg_ctx.hip (context forms, options), dpg_icp_api.hip (scan
 // store, batched and single ICP, covariance), dpg_gn_api.hip (pose graph, marginals) and
 // dpg_sweep.hip (re-linearisation sweep, dpg_add_node); the few functions they call across each
-// other are declared at the end.  Nothing here is exported from the library.
+// other are declared at the end.  The DPG store has a header of its own, dpg_dpg.h (dpg_store.hip, dpg_change.hip,
+// dpg_grid.hip, dpg_loc.hip; dpg_raster.h, dpg_change_plan.cpp).  Nothing here is exported from the library.
 // Every device array, pinned or host-mapped block, event, stream and solver handle of the layer is a
 // member that releases itself (DevBuf / PinBuf / MappedBuf, DevEvent, DevStream, CholPtr) of the
 // context, its batch graph (GnGraph), its collective thread (HostColl) or a child: the release calls
@@ -290,31 +291,6 @@ inline int join_cov(dpg_ctx* c) {
     c->cov_pending = false;
     return hipStreamWaitEvent(c->stream, c->ev[2].e, 0) == hipSuccess ? DPG_OK : DPG_ERR_HIP;
 }
-
-// Localisation in the active map (dpg_loc.hip): the field, its pooled form and the search buffers.
-// A member of the DPG store (dpg_change.hip), empty until the first request.
-struct LocRec { int32_t score, a, dx, dy; };   // a scored candidate; score < 0: none
-struct DpgLoc {
-    DevBuf<uint8_t> field, pool_tmp, pooled;   // F [h][w], the row-pooled F, P [h + s - 1][w + s - 1]
-    DevBuf<float> rot, cloud;                  // [A][2], [n_pts][2]
-    DevBuf<int2> keys;                         // [A][n_pts] field indices of the points at shift (-hx, -hy)
-    DevBuf<int32_t> vol;                       // [A][nby][nbx] bounds; the score volume of the diagnostic
-    DevBuf<int2> tile_best, seeds, entries;    // per (angle, tile) and per angle (bound, block); (a, block) lists
-    DevBuf<LocRec> partial, rec;               // per workgroup bests of a fine launch; [0] seeds', [1] overall, [2] at the guess
-    DevBuf<uint32_t> counter;                  // the frontier's size
-    std::vector<int8_t> occ_host;              // where dpg_occupancy_grid's host copy lands
-    DevEvent ev[4];
-};
-// what dpg_loc.hip needs of a store (dpg_change.hip fills it in; occ = the grid's device bytes of the
-// last dpg_occupancy_grid that asked for them)
-struct DpgLocView {
-    dpg_ctx* ctx;
-    hipStream_t stream;
-    int device;
-    const int8_t* occ;
-    DpgLoc* loc;
-};
-void dpg_dpg_loc_view(dpg_dpg* d, DpgLocView* v);
 
 // ---- across the layer's files ----
 extern dpg_ctx* g_default_ctx;   // icp_cov_calculate / icp_cov_sandwich without a context (dpg_ctx.hip)

@@ -31,7 +31,7 @@
 
 #include <cmath>
 
-#include "dpg_ctx.h"
+#include "dpg_raster.h"
 
 namespace {
 
@@ -92,15 +92,6 @@ __global__ __launch_bounds__(kT) void loc_pool_kernel(const uint8_t* in, uint8_t
         best = max(best, (int)in[(int64_t)y * wi + x]);   // 0 <= x < wi, 0 <= y < hi
     }
     out[c] = (uint8_t)best;
-}
-
-// round((double)v / res) when the point counts (finite, |v / res| < 2^29)
-__device__ __forceinline__ bool cell_key(float x, float y, double res, int& kx, int& ky) {
-    const double dx = (double)x / res, dy = (double)y / res;
-    if (!(fabs(dx) < 536870912.0) || !(fabs(dy) < 536870912.0)) return false;
-    kx = (int)round(dx);
-    ky = (int)round(dy);
-    return true;
 }
 
 // keys[a][i] = (kx + ox, ky + oy) with (ox, oy) = (cx - hx - x0, cy - hy - y0): the point's field
@@ -307,10 +298,6 @@ unsigned blocks_for(int64_t n) { return (unsigned)std::max<int64_t>((n + kT - 1)
 
 // a request as the host sees it
 struct Plan {
-    dpg_loc_params P;
-    double res;
-    int32_t box[4];
-    int64_t cells;
     int32_t cx, cy;
     int32_t A;
     int64_t n_blocks;   // A * nblk
@@ -324,73 +311,58 @@ bool host_key(float v, double res, int32_t& k) {
     return true;
 }
 
-int check_store(dpg_dpg* d, int64_t V, const float* est, const dpg_loc_params* p, const char* who, DpgLocView& v) {
+int check_store(dpg_dpg* d, int64_t V, const float* est, const dpg_loc_params* p, const char* who) {
     if (!d || !est || !p) return fail(DPG_ERR_ARG, "%s: a NULL argument", who);
-    dpg_dpg_loc_view(d, &v);
-    if (is_multi(v.ctx)) return fail(DPG_ERR_STATE, "%s runs on a single-device context", who);
+    if (is_multi(d->ctx)) return fail(DPG_ERR_STATE, "%s runs on a single-device context", who);
     if (dpg_loc_params_check(p)) return fail(DPG_ERR_ARG, "%s: a parameter out of range", who);
     if (V <= 0) return fail(DPG_ERR_ARG, "%s: n_nodes out of range", who);
     return DPG_OK;
 }
 
-// the grid of the active nodes on the device (its own call and buffers), then F and, for shift >= 0,
-// P at that shift; ev[0] .. ev[1] bracket the kernels launched here and *ms_grid is the grid's own
-int build_field(dpg_dpg* d, int64_t V, const float* est, const dpg_loc_params& P, int shift, DpgLocView& v, int32_t box[4],
-                double* res_out, double* ms_grid) {
-    dpg_grid_params gp;
-    dpg_grid_params_default(&gp);
-    gp.resolution = P.resolution;
-    gp.max_cells = P.max_cells;
-    gp.margin_cells = P.margin_cells;
+// the plan of the grid the field is taken from (dpg_grid.hip), under the localiser's parameters
+int plan_grid(dpg_dpg* d, int64_t V, const float* est, const dpg_loc_params& P, GridPlan& gp) {
+    dpg_grid_params g;
+    dpg_grid_params_default(&g);
+    g.resolution = P.resolution; g.max_cells = P.max_cells; g.margin_cells = P.margin_cells;
+    return grid_plan(d, V, est, g, gp);
+}
+
+// the planned grid (cells > 0) on the device, then F from its occupancy bytes and, for shift > 0, P
+// at that shift; ev[0] .. ev[1] bracket the kernels launched here and *ms_grid is the grid's own
+int build_field(dpg_dpg* d, const GridPlan& gp, const dpg_loc_params& P, int shift, double* ms_grid) {
     dpg_grid_info info;
-    int rc = dpg_occupancy_grid(d, V, est, &gp, nullptr, nullptr, nullptr, 0, &info);   // the plan
+    int rc = grid_run(d, gp, true, &info);
     if (rc) return rc;
-    box[0] = info.x0; box[1] = info.y0; box[2] = info.w; box[3] = info.h;
-    *res_out = info.resolution;
-    *ms_grid = 0.0;
-    const int64_t cells = (int64_t)info.w * info.h;
-    if (cells == 0) return DPG_OK;
-    DpgLoc& L = *v.loc;
-    if (L.occ_host.size() < (size_t)cells) L.occ_host.resize((size_t)cells);
-    if ((rc = dpg_occupancy_grid(d, V, est, &gp, nullptr, nullptr, L.occ_host.data(), cells, &info))) return rc;
-    if (info.w != box[2] || info.h != box[3]) return fail(DPG_ERR_STATE, "the grid's box changed between its plan and its run");
     *ms_grid = info.ms_kernels;
-    dpg_dpg_loc_view(d, &v);   // the grid's device bytes (its buffer may have been regrown)
-    const int32_t w = box[2], h = box[3], s = shift > 0 ? 1 << shift : 1;
+    DpgLoc& L = d->loc;
+    const int32_t w = gp.box[2], h = gp.box[3], s = shift > 0 ? 1 << shift : 1;
     const int64_t pw = (int64_t)w + s - 1, ph = (int64_t)h + s - 1;
     for (DevEvent& e : L.ev)
         if (e.ensure(hipEventDefault)) return fail(DPG_ERR_HIP, "hipEventCreate failed");
-    if (L.field.reserve((size_t)cells) || (shift > 0 && (L.pool_tmp.reserve((size_t)(pw * h)) || L.pooled.reserve((size_t)(pw * ph)))))
-        return fail(DPG_ERR_HIP, "out of device memory for a field of %lld cells", (long long)cells);
+    if (L.field.reserve((size_t)gp.cells) || (shift > 0 && (L.pool_tmp.reserve((size_t)(pw * h)) || L.pooled.reserve((size_t)(pw * ph)))))
+        return fail(DPG_ERR_HIP, "out of device memory for a field of %lld cells", (long long)gp.cells);
     Stencil st;
     memset(&st, 0, sizeof(st));
     dpg_csm_params cp;
     dpg_csm_params_default(&cp);
-    cp.resolution = (float)info.resolution;
-    cp.sigma = P.sigma;
-    cp.kernel_radius = P.kernel_radius;
+    cp.resolution = (float)gp.res; cp.sigma = P.sigma; cp.kernel_radius = P.kernel_radius;
     if (dpg_csm_lut(&cp, st.lut)) return fail(DPG_ERR_ARG, "the resolution is not a positive float");
-    st.R = P.kernel_radius;
-    st.occupied_min = P.occupied_min;
-    HIP_TRY(hipEventRecord(L.ev[0].e, v.stream));
-    loc_field_kernel<<<blocks_for(cells), kT, 0, v.stream>>>(v.occ, L.field.p, w, h, st);
+    st.R = P.kernel_radius; st.occupied_min = P.occupied_min;
+    HIP_TRY(hipEventRecord(L.ev[0].e, d->s));
+    loc_field_kernel<<<blocks_for(gp.cells), kT, 0, d->s>>>(d->d_occ_out.p, L.field.p, w, h, st);
     HIP_TRY(hipGetLastError());
     if (shift > 0) {
-        loc_pool_kernel<true><<<blocks_for(pw * h), kT, 0, v.stream>>>(L.field.p, L.pool_tmp.p, w, h, s);
+        loc_pool_kernel<true><<<blocks_for(pw * h), kT, 0, d->s>>>(L.field.p, L.pool_tmp.p, w, h, s);
         HIP_TRY(hipGetLastError());
-        loc_pool_kernel<false><<<blocks_for(pw * ph), kT, 0, v.stream>>>(L.pool_tmp.p, L.pooled.p, (int32_t)pw, h, s);
+        loc_pool_kernel<false><<<blocks_for(pw * ph), kT, 0, d->s>>>(L.pool_tmp.p, L.pooled.p, (int32_t)pw, h, s);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(L.ev[1].e, v.stream));
+    HIP_TRY(hipEventRecord(L.ev[1].e, d->s));
     return DPG_OK;
 }
 
 int make_plan(const dpg_loc_params& P, double res, const int32_t box[4], int64_t n_pts, const float guess[3], const char* who,
               Plan& pl) {
-    pl.P = P;
-    pl.res = res;
-    memcpy(pl.box, box, sizeof(pl.box));
-    pl.cells = (int64_t)box[2] * box[3];
     if (!host_key(guess[0], res, pl.cx) || !host_key(guess[1], res, pl.cy) || !std::isfinite(guess[2]))
         return fail(DPG_ERR_ARG, "%s: the guess is not finite or its cell key is beyond 2^29", who);
     Dims& g = pl.g;
@@ -420,8 +392,7 @@ enum Mode { kLocalize, kBounds, kScores };
 // the whole call; out: the bound volume (kBounds) or the score volume (kScores)
 int run(dpg_dpg* d, int64_t V, const float* est, const float* cloud, int64_t n_pts, const float guess[3],
         const dpg_loc_params* p, Mode mode, dpg_loc_result* result, int32_t* out, int64_t cap, const char* who) {
-    DpgLocView v;
-    int rc = check_store(d, V, est, p, who, v);
+    int rc = check_store(d, V, est, p, who);
     if (rc) return rc;
     if (n_pts < 0 || n_pts > (int64_t)1 << 23 || (n_pts > 0 && !cloud) || !guess)
         return fail(DPG_ERR_ARG, "%s: n_pts outside 0 .. 2^23, or a NULL argument", who);
@@ -437,9 +408,11 @@ int run(dpg_dpg* d, int64_t V, const float* est, const float* cloud, int64_t n_p
         if ((mode != kBounds && (mode == kScores ? nb : std::min<int64_t>(nb, P.max_refine_blocks)) * s * s > kItemMax))
             return fail(DPG_ERR_SIZE, "%s: more than 2^36 candidates to score in one launch", who);
     }
-    int32_t box[4];
-    double res = 0.0, ms_grid = 0.0;
-    if ((rc = build_field(d, V, est, P, P.coarse_shift, v, box, &res, &ms_grid))) return rc;
+    GridPlan gp;
+    double ms_grid = 0.0;
+    if ((rc = plan_grid(d, V, est, P, gp)) || (gp.cells > 0 && (rc = build_field(d, gp, P, P.coarse_shift, &ms_grid)))) return rc;
+    const int32_t* box = gp.box;
+    const double res = gp.res;
     Plan pl;
     if ((rc = make_plan(P, res, box, n_pts, guess, who, pl))) return rc;
     const Dims& g = pl.g;
@@ -448,21 +421,20 @@ int run(dpg_dpg* d, int64_t V, const float* est, const float* cloud, int64_t n_p
 
     dpg_loc_result r;
     memset(&r, 0, sizeof(r));
-    memcpy(r.box, box, sizeof(box));
+    memcpy(r.box, box, sizeof(r.box));
     r.n_pts = (int32_t)n_pts;
     r.n_seeds = (int32_t)A;
     r.n_blocks = pl.n_blocks;
     LocRec win = {0, P.half_a, 0, 0};   // the winner of an all-zero volume
-    if (pl.cells == 0) {
+    if (gp.cells == 0) {
         // no active node, no field: every bound and score is 0 and nothing is launched
         if (mode == kBounds) memset(out, 0, sizeof(int32_t) * (size_t)pl.n_blocks);
         if (mode == kScores) memset(out, 0, sizeof(int32_t) * (size_t)(A * Wx * Wy));
         if (mode != kLocalize) return DPG_OK;
         r.status = DPG_LOC_NO_OVERLAP;
     } else {
-        DpgLoc& L = *v.loc;
-        HIP_TRY(hipSetDevice(v.device));
-        hipStream_t s = v.stream;
+        DpgLoc& L = d->loc;
+        hipStream_t s = d->s;
         const int64_t cap_f = std::min<int64_t>(P.max_refine_blocks, pl.n_blocks);
         const int64_t items_seed = A << (2 * g.shift), items_front = cap_f << (2 * g.shift);
         const int64_t items_all = pl.n_blocks << (2 * g.shift);
@@ -584,35 +556,24 @@ int dpg_map_localize_scores(dpg_dpg* d, int64_t V, const float* est, const float
 
 int dpg_map_field(dpg_dpg* d, int64_t V, const float* est, const dpg_loc_params* p, int32_t shift, uint8_t* out, int64_t cap,
                   int32_t box[4]) {
-    DpgLocView v;
-    int rc = check_store(d, V, est, p, "dpg_map_field", v);
+    int rc = check_store(d, V, est, p, "dpg_map_field");
     if (rc) return rc;
     if (shift > 5) return fail(DPG_ERR_ARG, "dpg_map_field: shift above 5");
-    int32_t bx[4];
-    double res = 0.0, ms = 0.0;
-    if (!out) {   // plan only
-        dpg_grid_params gp;
-        dpg_grid_params_default(&gp);
-        gp.resolution = p->resolution;
-        gp.max_cells = p->max_cells;
-        gp.margin_cells = p->margin_cells;
-        dpg_grid_info info;
-        if ((rc = dpg_occupancy_grid(d, V, est, &gp, nullptr, nullptr, nullptr, 0, &info))) return rc;
-        if (box) { box[0] = info.x0; box[1] = info.y0; box[2] = info.w; box[3] = info.h; }
-        return DPG_OK;
+    GridPlan gp;
+    if ((rc = plan_grid(d, V, est, *p, gp))) return rc;
+    if (out) {
+        // the size first, from the plan, so that a small cap leaves nothing launched or written
+        const int64_t s = shift > 0 ? (int64_t)1 << shift : 1;
+        const int64_t n = gp.cells == 0 ? 0 : shift > 0 ? (gp.box[2] + s - 1) * (gp.box[3] + s - 1) : gp.cells;
+        if (cap < n) return fail(DPG_ERR_SIZE, "dpg_map_field: out holds %lld bytes, the field has %lld", (long long)cap, (long long)n);
+        if (n > 0) {
+            double ms = 0.0;
+            if ((rc = build_field(d, gp, *p, shift, &ms))) return rc;
+            HIP_TRY(hipMemcpyAsync(out, shift > 0 ? d->loc.pooled.p : d->loc.field.p, (size_t)n, hipMemcpyDeviceToHost, d->s));
+            HIP_TRY(hipStreamSynchronize(d->s));
+        }
     }
-    // the size first, from the plan, so that a small cap leaves nothing launched or written
-    if ((rc = dpg_map_field(d, V, est, p, shift, nullptr, 0, bx))) return rc;
-    const int64_t s = shift > 0 ? (int64_t)1 << shift : 1;
-    const int64_t cells = (int64_t)bx[2] * bx[3];
-    const int64_t n = cells == 0 ? 0 : shift > 0 ? (bx[2] + s - 1) * (bx[3] + s - 1) : cells;
-    if (cap < n) return fail(DPG_ERR_SIZE, "dpg_map_field: out holds %lld bytes, the field has %lld", (long long)cap, (long long)n);
-    if ((rc = build_field(d, V, est, *p, shift, v, bx, &res, &ms))) return rc;
-    if (box) memcpy(box, bx, sizeof(bx));
-    if (n == 0) return DPG_OK;
-    HIP_TRY(hipSetDevice(v.device));
-    HIP_TRY(hipMemcpyAsync(out, shift > 0 ? v.loc->pooled.p : v.loc->field.p, (size_t)n, hipMemcpyDeviceToHost, v.stream));
-    HIP_TRY(hipStreamSynchronize(v.stream));
+    if (box) memcpy(box, gp.box, sizeof(gp.box));
     return DPG_OK;
 }
 

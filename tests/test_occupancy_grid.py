@@ -1,4 +1,4 @@
-"""Occupancy grid of the active pose graph on the GPU (dpg_occupancy_grid, csrc/dpg_change.hip)
+"""Occupancy grid of the active pose graph on the GPU (dpg_occupancy_grid, csrc/dpg_grid.hip)
 against the numpy restatement tests/occ_grid_ref.py: hits, misses and the occupancy byte of EVERY
 cell of the returned box are equal, no tolerance; every cell the reference marks lies inside the box
 and the kernel reports no sample outside it.  The reference takes the device's own lidar positions

@@ -4,7 +4,9 @@
 // synthetic workload generator (csrc/dpg_synth.c), the symbolic Cholesky analysis, full and
 // incremental (csrc/dpg_chol_sym.cpp), and the GPU solver's host planner (csrc/dpg_chol_plan.cpp:
 // its tables are followed by the kernels without bounds checks; its pick of the fronts a partial
-// refactorization keeps, and of the runs that move them, against the pick's contract), driven through a small
+// refactorization keeps, and of the runs that move them, against the pick's contract) and change
+// detection's host plan (csrc/dpg_change_plan.cpp: window reuse and bit-plane bookkeeping against
+// values worked out by hand), driven through a small
 // end-to-end workload: scans -> clouds -> batched ICP + covariance -> factors -> Gauss-Newton ->
 // symbolic analysis -> solver plans -> DPG change detection over two passes; the owning buffer
 // template of the GPU layer (csrc/dpg_buf.h) over host memory; and the pose graphs' contribution
@@ -15,9 +17,12 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
+#include <initializer_list>
 #include <vector>
 
 #include "../dpg-slam_amd/csrc/dpg_buf.h"
+#include "../dpg-slam_amd/csrc/dpg_change_plan.h"
 #include "../dpg-slam_amd/csrc/dpg_chol.h"
 #include "../dpg-slam_amd/csrc/dpg_chol_plan.h"
 #include "../dpg-slam_amd/csrc/dpg_internal.h"
@@ -394,8 +399,96 @@ static int lists_checks() {
     return 0;
 }
 
+// dpg_change_plan, the host half of dpg_execute_dpg_chain, against values worked out by hand.  No
+// laser offset, resolution 0.05, every node's largest range 2, node v at (0.125 + 0.5 v, 0.125, 0):
+// a chain node's rays need the keys [10 v - 37.5, 10 v + 42.5] x [-37.5, 42.5], widened by 4 cells
+// (need) and, for a new window, by ceil(4 / 0.05) = 80 more on every side.
+static bool same_kept(const ChangeKept& a, const ChangeKept& b) {
+    return a.win.x0 == b.win.x0 && a.win.y0 == b.win.y0 && a.win.w == b.win.w && a.win.h == b.win.h && a.win_valid == b.win_valid &&
+           memcmp(a.slot_node, b.slot_node, sizeof(a.slot_node)) == 0 && memcmp(a.slot_pose, b.slot_pose, sizeof(a.slot_pose)) == 0;
+}
+static bool same_ints(const int32_t* got, std::initializer_list<int32_t> want) { return std::equal(want.begin(), want.end(), got); }
+static bool same_box(const Box& b, int32_t x0, int32_t y0, int32_t w, int32_t h) { return b.x0 == x0 && b.y0 == y0 && b.w == w && b.h == h; }
+
+static int change_plan_checks() {
+    dpg_change_params p;
+    memset(&p, 0, sizeof(p));
+    p.num_sectors = 5;
+    p.current_pose_chain_len = 3;
+    p.num_bins_for_change_detection = 36;
+    p.occ_grid_resolution = 0.05;
+    p.distance_threshold_for_local_submap_nodes = 5.0f;
+    const int N = 20;
+    std::vector<float> est(3 * N, 0.f), rmax(N, 2.0f);
+    std::vector<uint8_t> act(N, 1);
+    for (int v = 0; v < N; ++v) { est[3 * v] = 0.125f + 0.5f * (float)v; est[3 * v + 1] = 0.125f; }
+    ChangePlan pl;
+    ChangeKept k0, k1, k2;
+    // (a) three calls, one new node each: the window of the first is reused, the two surviving chain
+    // nodes keep their planes, only the new node is rasterised
+    REQUIRE(dpg_change_plan(p, 6, 3, est.data(), nullptr, act.data(), rmax.data(), k0, pl) == DPG_OK);
+    REQUIRE(pl.n_chain == 3 && same_ints(pl.chain, {3, 4, 5}) && pl.cand.size() == 3 && same_ints(pl.cand.data(), {0, 1, 2}));
+    REQUIRE(!pl.reuse && same_box(pl.need, -12, -42, 110, 90) && same_box(pl.win, -92, -122, 270, 250) && pl.chain_sep == 0);
+    REQUIRE(same_ints(pl.slot, {0, 1, 2}) && pl.n_rast == 3 && same_ints(pl.rast, {0, 1, 2}) && pl.keep_mask == 0u && pl.chain_bits == 0x3fu);
+    REQUIRE(pl.cframe[1][0] == 2.125f && pl.cframe[1][1] == 0.125f && pl.cframe[1][2] == 1.f && pl.cframe[1][3] == 0.f);
+    REQUIRE(pl.kept.win_valid && same_ints(pl.kept.slot_node, {3, 4, 5, -1}) && pl.kept.slot_pose[2][0] == 2.625f && same_kept(k0, ChangeKept()));
+    k1 = pl.kept;
+    REQUIRE(dpg_change_plan(p, 7, 3, est.data(), nullptr, act.data(), rmax.data(), k1, pl) == DPG_OK);
+    REQUIRE(pl.reuse && same_box(pl.need, -2, -42, 110, 90) && same_box(pl.win, -92, -122, 270, 250) && same_ints(pl.chain, {4, 5, 6}));
+    REQUIRE(same_ints(pl.slot, {1, 2, 0}) && pl.n_rast == 1 && pl.rast[0] == 2 && pl.keep_mask == 0x3cu && pl.chain_bits == 0x3fu);
+    REQUIRE(same_ints(pl.kept.slot_node, {6, 4, 5, -1}));
+    k2 = pl.kept;
+    REQUIRE(dpg_change_plan(p, 8, 3, est.data(), nullptr, act.data(), rmax.data(), k2, pl) == DPG_OK);
+    REQUIRE(pl.reuse && same_box(pl.need, 8, -42, 110, 90) && same_ints(pl.slot, {2, 0, 1}) && pl.n_rast == 1 && pl.rast[0] == 2);
+    REQUIRE(pl.keep_mask == 0x33u && pl.chain_bits == 0x3fu && same_ints(pl.kept.slot_node, {6, 7, 5, -1}));
+    REQUIRE(pl.cand.size() == 5 && same_ints(pl.cand.data(), {0, 1, 2, 3, 4}));
+    // (b) the second call again, node 5's chain pose one ulp off: its plane is released, it is rasterised again
+    float cp[9];
+    memcpy(cp, &est[12], sizeof(cp));
+    cp[3] = nextafterf(cp[3], 100.f);
+    REQUIRE(dpg_change_plan(p, 7, 3, est.data(), cp, act.data(), rmax.data(), k1, pl) == DPG_OK);
+    REQUIRE(pl.reuse && pl.chain_sep == 1 && same_ints(pl.slot, {1, 0, 2}) && pl.n_rast == 2 && same_ints(pl.rast, {1, 2}));
+    REQUIRE(pl.keep_mask == 0x0cu && pl.chain_bits == 0x3fu && same_ints(pl.kept.slot_node, {5, 4, 6, -1}) && pl.kept.slot_pose[0][0] == cp[3]);
+    // (c) node 6 five metres further on: its box leaves the kept window, which is rebuilt
+    std::vector<float> far = est;
+    far[18] = 10.125f;
+    REQUIRE(dpg_change_plan(p, 7, 3, far.data(), nullptr, act.data(), rmax.data(), k1, pl) == DPG_OK);
+    REQUIRE(!pl.reuse && same_box(pl.need, -2, -42, 250, 90) && same_box(pl.win, -82, -122, 410, 250));
+    REQUIRE(same_ints(pl.slot, {0, 1, 2}) && pl.n_rast == 3 && same_ints(pl.rast, {0, 1, 2}) && pl.keep_mask == 0u);
+    REQUIRE(same_ints(pl.kept.slot_node, {4, 5, 6, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1}));
+    // (d) a chain of 15: every plane used, each once
+    p.current_pose_chain_len = 15;
+    REQUIRE(dpg_change_plan(p, 20, 20, est.data(), nullptr, act.data(), rmax.data(), k0, pl) == DPG_OK);
+    REQUIRE(pl.n_chain == 15 && pl.n_rast == 15 && pl.chain[0] == 5 && pl.chain[14] == 19 && pl.cand.empty() && pl.chain_bits == 0x3fffffffu);
+    for (int k = 0; k < 15; ++k) REQUIRE(pl.slot[k] == k && pl.rast[k] == k && pl.kept.slot_node[k] == 5 + k);
+    // (e) no current pass: an empty chain, no candidates, the kept state as it was
+    REQUIRE(dpg_change_plan(p, 20, 0, est.data(), nullptr, act.data(), rmax.data(), k1, pl) == DPG_OK);
+    REQUIRE(pl.n_chain == 0 && pl.n_rast == 0 && pl.cand.empty() && same_kept(pl.kept, k1));
+    // (f) the two errors; the caller's kept state is read only
+    p.current_pose_chain_len = 3;
+    const ChangeKept before = k1;
+    cp[3] = NAN;
+    REQUIRE(dpg_change_plan(p, 7, 3, est.data(), cp, act.data(), rmax.data(), k1, pl) == DPG_ERR_ARG && same_kept(k1, before));
+    std::vector<float> wide(N, 500.f);   // some 20000 x 20000 cells needed: above 2^28 with or without the margin
+    REQUIRE(dpg_change_plan(p, 7, 3, est.data(), nullptr, act.data(), wide.data(), k1, pl) == DPG_ERR_SIZE && same_kept(k1, before));
+    // (g) candidates of a chain at the origin: exactly at the threshold is taken (3-4-5), one ulp
+    // beyond it is not, an inactive node inside the radius is not
+    std::vector<float> g(3 * 8, 0.f);
+    g[0] = 3.f; g[1] = 4.f;                           // node 0: sqrtf(9 + 16) = 5 <= 5
+    g[3] = 1.f; g[4] = 1.f;                           // node 1: inside, inactive
+    g[6] = 100.f;                                     // node 2: far
+    g[9] = 3.f; g[10] = nextafterf(4.f, 5.f);         // node 3: sqrtf(25.000004) > 5
+    g[12] = -3.f; g[13] = -4.f;                       // node 4: exactly 5 again
+    act[1] = 0;
+    REQUIRE(dpg_change_plan(p, 8, 3, g.data(), nullptr, act.data(), rmax.data(), k0, pl) == DPG_OK);
+    REQUIRE(pl.cand.size() == 2 && same_ints(pl.cand.data(), {0, 4}) && same_ints(pl.chain, {5, 6, 7}));
+    printf("change plan ok: reuse, released plane, rebuild, 15 planes, empty chain, errors, candidates\n");
+    return 0;
+}
+
 int main() {
     REQUIRE(buffer_checks() == 0);
+    REQUIRE(change_plan_checks() == 0);
     const int V = 24, NB = 720;
     const float W = 20.f, amin = (float)-M_PI, amax = (float)M_PI, rmax = 12.f;
     std::vector<float> segs(4 * 512);
