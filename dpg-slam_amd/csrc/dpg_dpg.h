@@ -1,5 +1,6 @@
 // dpg_dpg.h -- the DPG node store (struct dpg_dpg) as dpg_store.hip, dpg_change.hip, dpg_grid.hip and
-// dpg_loc.hip see it (private, C++).  Every array releases itself; kernels take the view DS (make_ds).
+// dpg_loc.hip see it, and the frozen map (struct dpg_fmap) of dpg_loc.hip and dpg_track.hip (private,
+// C++).  Every array releases itself; kernels take the view DS (make_ds).
 #ifndef DPG_DPG_H
 #define DPG_DPG_H
 
@@ -106,6 +107,35 @@ struct dpg_dpg {
     DpgLoc loc;                               // dpg_map_localize's field and search buffers (dpg_loc.hip)
     PinBuf<Ctl> h_ctl;
     DevEvent ev[2];
+};
+
+// A frozen map (dpg_fmap_*): a likelihood field with its box and resolution in buffers of its own, a
+// child of the context that keeps no reference to the store it was taken from.  dpg_loc.hip creates,
+// saves, loads and searches it; dpg_track.hip tracks batches of scans against it.
+struct TrackRec { LocRec win; int32_t score_at_guess, pad[3]; };   // a scan's record as the device leaves it
+struct dpg_fmap {
+    dpg_ctx* ctx = nullptr;
+    hipStream_t s = nullptr;
+    int device = 0;
+    int32_t box[4] = {0, 0, 0, 0};            // x0, y0, w, h
+    double res = 0.0;
+    float sigma = 0.f;                        // how F was made: metadata, not read by any search
+    int32_t kernel_radius = 0, occupied_min = 0;
+    DevBuf<uint8_t> field;                    // F [h][w]
+    DevBuf<uint8_t> pooled[6];                // P at shift 1 .. 5, pooled from F at first use and kept
+    bool have_pooled[6] = {false, false, false, false, false, false};
+    DpgLoc loc;                               // dpg_fmap_localize's search buffers (its field and pooled stay empty)
+    // dpg_fmap_track: the call's one upload (pinned, then device), the (scan, angle) bests, the scores at
+    // the guesses and the records
+    PinBuf<unsigned char> h_in;
+    DevBuf<unsigned char> d_in;
+    DevBuf<LocRec> part;
+    DevBuf<int32_t> at_guess;
+    DevBuf<TrackRec> recs;
+    PinBuf<TrackRec> h_recs;
+    DevEvent track_ev[2];                     // around the two launches of the last call
+    float track_ms = 0.f;
+    int64_t cells() const { return (int64_t)box[2] * box[3]; }
 };
 
 // ---- dpg_store.hip ----

@@ -255,6 +255,43 @@ int dpg_loc_rotations(float guess_theta, const dpg_loc_params* p, float* rot_out
     return DPG_OK;
 }
 
+void dpg_track_params_default(dpg_track_params* p) {
+    if (!p) return;
+    p->half_x = 10;
+    p->half_y = 10;
+    p->half_a = 10;
+    p->angle_step = (float)(0.5 * M_PI / 180.0);
+}
+
+int dpg_track_params_check(const dpg_track_params* p) {
+    if (!p) return DPG_ERR_ARG;
+    if (p->half_x < 0 || p->half_x > 64 || p->half_y < 0 || p->half_y > 64 || p->half_a < 0 || p->half_a > 64) return DPG_ERR_ARG;
+    if (!(p->angle_step > 0.0f) || !isfinite(p->angle_step)) return DPG_ERR_ARG;
+    return DPG_OK;
+}
+
+/* the frozen map's file header (the layout is in dpg_slam_c.h); the host is little-endian */
+int dpg_fmap_header_check(const void* hdr64, int64_t file_bytes) {
+    if (!hdr64) return DPG_ERR_ARG;
+    const unsigned char* h = (const unsigned char*)hdr64;
+    uint32_t version;
+    double res;
+    int32_t box[4];
+    int64_t n_bytes;
+    if (memcmp(h, "DPGFMAP1", 8) != 0) return DPG_ERR_ARG;
+    memcpy(&version, h + 8, 4);
+    memcpy(&res, h + 24, 8);
+    memcpy(box, h + 32, 16);
+    memcpy(&n_bytes, h + 48, 8);
+    if (version != 1u) return DPG_ERR_ARG;
+    if (!(res > 0.0) || !isfinite(res)) return DPG_ERR_ARG;
+    if (box[2] < 0 || box[3] < 0 || (int64_t)box[2] * box[3] > (int64_t)1 << 25) return DPG_ERR_ARG;
+    if (n_bytes != (int64_t)box[2] * box[3] || file_bytes != DPG_FMAP_HEADER_SIZE + n_bytes) return DPG_ERR_ARG;
+    for (int i = 56; i < 64; ++i)
+        if (h[i]) return DPG_ERR_ARG;
+    return DPG_OK;
+}
+
 /* R9: odometry BetweenFactor from two odom_only_estimates (dpg_slam.cc:56-75). */
 int dpg_odometry_factor(const float odom_prev[3], const float odom_cur[3], int32_t i_prev, int32_t i_cur,
                         float transl_from_transl, float transl_from_rot, float rot_from_transl,

@@ -4,6 +4,9 @@
 // order, search and statuses -- is the comment above dpg_loc_params in include/dpg_slam_c.h; the host
 // halves (dpg_loc_params_default / _check, dpg_loc_rotations) are plain C in dpg_host.c, the
 // smoothing bytes are dpg_csm_lut's.  The reference has no such stage.
+// The same search runs on a frozen map (dpg_fmap_*, at the end of this file): a field kept in a
+// handle of its own; both callers fill a View and call search().  The helpers the tracker
+// (dpg_track.hip) shares -- the key rule, the winner's order and its tree -- are in dpg_loc_dev.h.
 //
 // Unlike the pair matcher (dpg_csm.hip) the table is the whole map, so it lives in global memory and
 // is gathered through L2; LDS holds only a chunk of the scan's keys.  Kernels, in launch order:
@@ -31,16 +34,16 @@
 
 #include <cmath>
 
-#include "dpg_raster.h"
+#include <stdio.h>
+
+#include "dpg_loc_dev.h"
 
 namespace {
 
-constexpr int kT = 256;               // threads per workgroup
-constexpr int kChunk = 2048;          // keys per LDS chunk (16 KiB)
+constexpr int kT = kLocT;             // threads per workgroup
+constexpr int kChunk = kLocChunk;     // keys per LDS chunk (16 KiB)
 constexpr int kTileX = 64, kTileY = 4;
 static_assert(kTileX * kTileY == kT, "a thread per block of the tile");
-constexpr int kKeyNone = -(1 << 30);  // key of a point that contributes nothing: no shift brings it to an index >= -(s - 1)
-constexpr int64_t kKeyLim = (int64_t)1 << 27;   // |key| beyond this reaches no cell of a box of <= 2^25 cells under any shift
 constexpr int64_t kVolMax = (int64_t)1 << 29;
 constexpr int64_t kItemMax = (int64_t)1 << 36;
 
@@ -101,17 +104,7 @@ __global__ __launch_bounds__(kT) void loc_keys_kernel(const float2* cloud, const
     const int i = blockIdx.x * kT + threadIdx.x;
     if (i >= n_pts) return;
     const int a = blockIdx.y;
-    const float c = rot[2 * a], s = rot[2 * a + 1];
-    const float2 p = cloud[i];
-    const float rx = (c * p.x) - (s * p.y);
-    const float ry = (s * p.x) + (c * p.y);
-    int2 k = make_int2(kKeyNone, kKeyNone);
-    int kx, ky;
-    if (cell_key(rx, ry, res, kx, ky)) {
-        const int64_t ux = (int64_t)kx + ox, uy = (int64_t)ky + oy;
-        if (ux >= -kKeyLim && ux <= kKeyLim && uy >= -kKeyLim && uy <= kKeyLim) k = make_int2((int)ux, (int)uy);
-    }
-    keys[(int64_t)a * n_pts + i] = k;   // a < A, i < n_pts
+    keys[(int64_t)a * n_pts + i] = loc_key(cloud[i], rot[2 * a], rot[2 * a + 1], res, ox, oy);   // a < A, i < n_pts
 }
 
 // the seed order: higher bound, then the block nearer the window's centre, then the smaller index
@@ -182,28 +175,6 @@ __global__ __launch_bounds__(kT) void loc_seed_kernel(Dims g, const int2* tile_b
         seeds[a] = best;                      // bound >= 0: every angle has a block
         entries[a] = make_int2(a, best.y);
     }
-}
-
-// the winner's order: higher score, then smaller |a - ha|, dx^2 + dy^2, a, dy, dx
-__device__ __forceinline__ bool rec_better(int ha, const LocRec& x, const LocRec& y) {
-    if (x.score != y.score) return x.score > y.score;
-    if (x.score < 0) return false;
-    const int ax = abs(x.a - ha), ay = abs(y.a - ha);
-    if (ax != ay) return ax < ay;
-    const int64_t dx = (int64_t)x.dx * x.dx + (int64_t)x.dy * x.dy, dy = (int64_t)y.dx * y.dx + (int64_t)y.dy * y.dy;
-    if (dx != dy) return dx < dy;
-    if (x.a != y.a) return x.a < y.a;
-    if (x.dy != y.dy) return x.dy < y.dy;
-    return x.dx < y.dx;
-}
-__device__ __forceinline__ LocRec rec_reduce(int ha, LocRec mine, LocRec* sh) {
-    sh[threadIdx.x] = mine;
-    __syncthreads();
-    for (int st = kT / 2; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st && rec_better(ha, sh[threadIdx.x + st], sh[threadIdx.x])) sh[threadIdx.x] = sh[threadIdx.x + st];
-        __syncthreads();
-    }
-    return sh[0];
 }
 
 // item = entry * s^2 + candidate; entries == NULL: entry e is block e % nblk of angle e / nblk.
@@ -293,6 +264,8 @@ __global__ __launch_bounds__(kT) void loc_point_kernel(Dims g, const int2* keys,
     }
     if (threadIdx.x == 0) *out = LocRec{s_sum[0], g.ha, 0, 0};
 }
+
+enum Mode { kLocalize, kBounds, kScores };
 
 unsigned blocks_for(int64_t n) { return (unsigned)std::max<int64_t>((n + kT - 1) / kT, 1); }
 
@@ -387,32 +360,69 @@ int make_plan(const dpg_loc_params& P, double res, const int32_t box[4], int64_t
     return DPG_OK;
 }
 
-enum Mode { kLocalize, kBounds, kScores };
+// What a search reads, filled by its two callers (the store's run() and dpg_fmap_localize): the field, its
+// pooled form at the request's coarse_shift (F itself at shift 0), box and resolution, the search
+// buffers and the stream.  built: L->ev[0] .. ev[1] bracket the kernels that made F and P for this call.
+struct View {
+    const uint8_t* F = nullptr;
+    const uint8_t* P = nullptr;
+    int32_t box[4] = {0, 0, 0, 0};
+    double res = 0.0;
+    int64_t cells = 0;
+    DpgLoc* L = nullptr;
+    hipStream_t s = nullptr;
+    bool built = false;
+    double ms_grid = 0.0;
+};
 
-// the whole call; out: the bound volume (kBounds) or the score volume (kScores)
+// the request's own checks, before anything is planned or launched
+int check_request(const float* cloud, int64_t n_pts, const float guess[3], const dpg_loc_params& P, Mode mode, int64_t cap,
+                  const char* who) {
+    if (n_pts < 0 || n_pts > (int64_t)1 << 23 || (n_pts > 0 && !cloud) || !guess)
+        return fail(DPG_ERR_ARG, "%s: n_pts outside 0 .. 2^23, or a NULL argument", who);
+    const int64_t Wx = 2 * (int64_t)P.half_x + 1, Wy = 2 * (int64_t)P.half_y + 1, A = 2 * (int64_t)P.half_a + 1;
+    // sizes that depend on the parameters alone come first: a DPG_ERR_SIZE leaves nothing launched
+    const int64_t s = (int64_t)1 << P.coarse_shift;
+    const int64_t nb = A * ((Wx + s - 1) / s) * ((Wy + s - 1) / s);
+    if (mode == kBounds && cap < nb) return fail(DPG_ERR_SIZE, "%s: out holds %lld bounds, the volume has %lld", who, (long long)cap, (long long)nb);
+    if (mode == kScores && (A * Wx * Wy > kVolMax || cap < A * Wx * Wy))
+        return fail(DPG_ERR_SIZE, "%s: out holds %lld scores, the volume has %lld (at most 2^29)", who, (long long)cap, (long long)(A * Wx * Wy));
+    if ((mode != kBounds && (mode == kScores ? nb : std::min<int64_t>(nb, P.max_refine_blocks)) * s * s > kItemMax))
+        return fail(DPG_ERR_SIZE, "%s: more than 2^36 candidates to score in one launch", who);
+    return DPG_OK;
+}
+
+int search(const View& v, const float* cloud, int64_t n_pts, const float guess[3], const dpg_loc_params& P, Mode mode,
+           dpg_loc_result* result, int32_t* out, const char* who);
+
+// the whole call on a store; out: the bound volume (kBounds) or the score volume (kScores)
 int run(dpg_dpg* d, int64_t V, const float* est, const float* cloud, int64_t n_pts, const float guess[3],
         const dpg_loc_params* p, Mode mode, dpg_loc_result* result, int32_t* out, int64_t cap, const char* who) {
     int rc = check_store(d, V, est, p, who);
     if (rc) return rc;
-    if (n_pts < 0 || n_pts > (int64_t)1 << 23 || (n_pts > 0 && !cloud) || !guess)
-        return fail(DPG_ERR_ARG, "%s: n_pts outside 0 .. 2^23, or a NULL argument", who);
     const dpg_loc_params P = *p;
-    const int64_t Wx = 2 * (int64_t)P.half_x + 1, Wy = 2 * (int64_t)P.half_y + 1, A = 2 * (int64_t)P.half_a + 1;
-    // sizes that depend on the parameters alone come first: a DPG_ERR_SIZE leaves nothing launched
-    {
-        const int64_t s = (int64_t)1 << P.coarse_shift;
-        const int64_t nb = A * ((Wx + s - 1) / s) * ((Wy + s - 1) / s);
-        if (mode == kBounds && cap < nb) return fail(DPG_ERR_SIZE, "%s: out holds %lld bounds, the volume has %lld", who, (long long)cap, (long long)nb);
-        if (mode == kScores && (A * Wx * Wy > kVolMax || cap < A * Wx * Wy))
-            return fail(DPG_ERR_SIZE, "%s: out holds %lld scores, the volume has %lld (at most 2^29)", who, (long long)cap, (long long)(A * Wx * Wy));
-        if ((mode != kBounds && (mode == kScores ? nb : std::min<int64_t>(nb, P.max_refine_blocks)) * s * s > kItemMax))
-            return fail(DPG_ERR_SIZE, "%s: more than 2^36 candidates to score in one launch", who);
-    }
+    if ((rc = check_request(cloud, n_pts, guess, P, mode, cap, who))) return rc;
     GridPlan gp;
-    double ms_grid = 0.0;
-    if ((rc = plan_grid(d, V, est, P, gp)) || (gp.cells > 0 && (rc = build_field(d, gp, P, P.coarse_shift, &ms_grid)))) return rc;
-    const int32_t* box = gp.box;
-    const double res = gp.res;
+    View v;
+    if ((rc = plan_grid(d, V, est, P, gp)) || (gp.cells > 0 && (rc = build_field(d, gp, P, P.coarse_shift, &v.ms_grid)))) return rc;
+    v.F = d->loc.field.p;
+    v.P = P.coarse_shift > 0 ? d->loc.pooled.p : d->loc.field.p;
+    memcpy(v.box, gp.box, sizeof(v.box));
+    v.res = gp.res;
+    v.cells = gp.cells;
+    v.L = &d->loc;
+    v.s = d->s;
+    v.built = gp.cells > 0;
+    return search(v, cloud, n_pts, guess, P, mode, result, out, who);
+}
+
+// the search of one request over a view
+int search(const View& v, const float* cloud, int64_t n_pts, const float guess[3], const dpg_loc_params& P, Mode mode,
+           dpg_loc_result* result, int32_t* out, const char* who) {
+    int rc;
+    const int64_t Wx = 2 * (int64_t)P.half_x + 1, Wy = 2 * (int64_t)P.half_y + 1, A = 2 * (int64_t)P.half_a + 1;
+    const int32_t* box = v.box;
+    const double res = v.res;
     Plan pl;
     if ((rc = make_plan(P, res, box, n_pts, guess, who, pl))) return rc;
     const Dims& g = pl.g;
@@ -426,15 +436,18 @@ int run(dpg_dpg* d, int64_t V, const float* est, const float* cloud, int64_t n_p
     r.n_seeds = (int32_t)A;
     r.n_blocks = pl.n_blocks;
     LocRec win = {0, P.half_a, 0, 0};   // the winner of an all-zero volume
-    if (gp.cells == 0) {
+    if (v.cells == 0) {
         // no active node, no field: every bound and score is 0 and nothing is launched
         if (mode == kBounds) memset(out, 0, sizeof(int32_t) * (size_t)pl.n_blocks);
         if (mode == kScores) memset(out, 0, sizeof(int32_t) * (size_t)(A * Wx * Wy));
         if (mode != kLocalize) return DPG_OK;
         r.status = DPG_LOC_NO_OVERLAP;
     } else {
-        DpgLoc& L = d->loc;
-        hipStream_t s = d->s;
+        DpgLoc& L = *v.L;
+        hipStream_t s = v.s;
+        for (DevEvent& e : L.ev)
+            if (e.ensure(hipEventDefault)) return fail(DPG_ERR_HIP, "hipEventCreate failed");
+        if (!v.built) HIP_TRY(hipEventRecord(L.ev[1].e, s));   // ms_bound starts here when no field precedes it
         const int64_t cap_f = std::min<int64_t>(P.max_refine_blocks, pl.n_blocks);
         const int64_t items_seed = A << (2 * g.shift), items_front = cap_f << (2 * g.shift);
         const int64_t items_all = pl.n_blocks << (2 * g.shift);
@@ -448,13 +461,13 @@ int run(dpg_dpg* d, int64_t V, const float* est, const float* cloud, int64_t n_p
         HIP_TRY(hipMemcpyAsync(L.rot.p, rot.data(), sizeof(float) * 2 * A, hipMemcpyHostToDevice, s));
         if (n_pts > 0) HIP_TRY(hipMemcpyAsync(L.cloud.p, cloud, sizeof(float) * 2 * n_pts, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemsetAsync(L.counter.p, 0, sizeof(uint32_t) * 4, s));
-        const uint8_t* Pd = g.shift > 0 ? L.pooled.p : L.field.p;
+        const uint8_t* Pd = v.P;
         const int64_t ox = (int64_t)pl.cx - P.half_x - box[0], oy = (int64_t)pl.cy - P.half_y - box[1];
         loc_keys_kernel<<<dim3(blocks_for(n_pts), (unsigned)A), kT, 0, s>>>(reinterpret_cast<const float2*>(L.cloud.p), L.rot.p,
                                                                           L.keys.p, g.n_pts, res, ox, oy);
         HIP_TRY(hipGetLastError());
         if (mode == kScores) {
-            loc_fine_kernel<<<blocks_for(items_all), kT, 0, s>>>(g, L.keys.p, L.field.p, nullptr, nullptr, pl.n_blocks, L.vol.p,
+            loc_fine_kernel<<<blocks_for(items_all), kT, 0, s>>>(g, L.keys.p, v.F, nullptr, nullptr, pl.n_blocks, L.vol.p,
                                                                L.partial.p, nullptr);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpyAsync(out, L.vol.p, sizeof(int32_t) * (size_t)(A * Wx * Wy), hipMemcpyDeviceToHost, s));
@@ -474,7 +487,7 @@ int run(dpg_dpg* d, int64_t V, const float* est, const float* cloud, int64_t n_p
         // counter words: [0] the frontier's size, [2..3] one 64-bit count of scored candidates
         unsigned long long* n_cand = reinterpret_cast<unsigned long long*>(L.counter.p + 2);
         const unsigned nb_seed = blocks_for(items_seed), nb_front = blocks_for(items_front);
-        loc_fine_kernel<<<nb_seed, kT, 0, s>>>(g, L.keys.p, L.field.p, L.entries.p, nullptr, A, nullptr, L.partial.p, n_cand);
+        loc_fine_kernel<<<nb_seed, kT, 0, s>>>(g, L.keys.p, v.F, L.entries.p, nullptr, A, nullptr, L.partial.p, n_cand);
         HIP_TRY(hipGetLastError());
         loc_reduce_kernel<<<1, kT, 0, s>>>(L.partial.p, nb_seed, nullptr, L.rec.p, P.half_a);
         HIP_TRY(hipGetLastError());
@@ -483,12 +496,12 @@ int run(dpg_dpg* d, int64_t V, const float* est, const float* cloud, int64_t n_p
         loc_frontier_kernel<<<blocks_for(pl.n_blocks), kT, 0, s>>>(L.vol.p, pl.n_blocks, g.nblk, L.rec.p, L.entries.p + A, cap_f,
                                                                   L.counter.p);
         HIP_TRY(hipGetLastError());
-        loc_fine_kernel<<<nb_front, kT, 0, s>>>(g, L.keys.p, L.field.p, L.entries.p + A, L.counter.p, cap_f, nullptr,
+        loc_fine_kernel<<<nb_front, kT, 0, s>>>(g, L.keys.p, v.F, L.entries.p + A, L.counter.p, cap_f, nullptr,
                                               L.partial.p + nb_seed, n_cand);
         HIP_TRY(hipGetLastError());
         loc_reduce_kernel<<<1, kT, 0, s>>>(L.partial.p + nb_seed, nb_front, L.rec.p, L.rec.p + 1, P.half_a);
         HIP_TRY(hipGetLastError());
-        loc_point_kernel<<<1, kT, 0, s>>>(g, L.keys.p, L.field.p, L.rec.p + 2);
+        loc_point_kernel<<<1, kT, 0, s>>>(g, L.keys.p, v.F, L.rec.p + 2);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(L.ev[3].e, s));
         LocRec rec[3];
@@ -511,10 +524,10 @@ int run(dpg_dpg* d, int64_t V, const float* est, const float* cloud, int64_t n_p
         if (win.score == 0 && (seed_max == 0 || !overflow)) r.status = DPG_LOC_NO_OVERLAP;
         else r.status = overflow ? DPG_LOC_UNPROVEN : DPG_LOC_OK;
         float ms[3] = {0.f, 0.f, 0.f};
-        (void)hipEventElapsedTime(&ms[0], L.ev[0].e, L.ev[1].e);
+        if (v.built) (void)hipEventElapsedTime(&ms[0], L.ev[0].e, L.ev[1].e);
         (void)hipEventElapsedTime(&ms[1], L.ev[1].e, L.ev[2].e);
         (void)hipEventElapsedTime(&ms[2], L.ev[2].e, L.ev[3].e);
-        r.ms_field = ms_grid + ms[0];
+        r.ms_field = v.ms_grid + ms[0];   // 0 when this call built nothing
         r.ms_bound = ms[1];
         r.ms_fine = ms[2];
         r.ms_kernels = r.ms_field + r.ms_bound + r.ms_fine;
@@ -532,9 +545,204 @@ int run(dpg_dpg* d, int64_t V, const float* est, const float* cloud, int64_t n_p
     return DPG_OK;
 }
 
+// ---- the frozen map (struct dpg_fmap, dpg_dpg.h) ----
+constexpr int64_t kFmapCells = (int64_t)1 << 25;   // the grid's max_cells ceiling (dpg_loc_params_check)
+
+// an adopted map with F allocated and not yet written, or NULL with the thread's error set
+dpg_fmap* fmap_new(dpg_ctx* ctx, const int32_t box[4], double res, float sigma, int32_t kernel_radius, int32_t occupied_min,
+                   const char* who) {
+    if (!ctx || !box) { fail(DPG_ERR_ARG, "%s: a NULL argument", who); return nullptr; }
+    if (is_multi(ctx)) { fail(DPG_ERR_STATE, "%s: a frozen map lives on a single-device context", who); return nullptr; }
+    if (!(res > 0.0) || !std::isfinite(res) || box[2] < 0 || box[3] < 0 || (int64_t)box[2] * box[3] > kFmapCells) {
+        fail(DPG_ERR_ARG, "%s: res must be finite and > 0, w and h >= 0 and w h <= 2^25", who);
+        return nullptr;
+    }
+    dpg_fmap* m = new dpg_fmap();
+    m->ctx = ctx; m->s = ctx->stream; m->device = ctx->device;
+    memcpy(m->box, box, sizeof(m->box));
+    m->res = res; m->sigma = sigma; m->kernel_radius = kernel_radius; m->occupied_min = occupied_min;
+    if (hipSetDevice(m->device) != hipSuccess || m->field.reserve((size_t)m->cells())) {
+        delete m;
+        fail(DPG_ERR_HIP, "%s: out of device memory for a field of %lld cells", who, (long long)((int64_t)box[2] * box[3]));
+        return nullptr;
+    }
+    dpg_ctx_adopt(ctx, m, [](void* x) { dpg_fmap_destroy(static_cast<dpg_fmap*>(x)); });
+    return m;
+}
+
+// P at `shift` (1 .. 5) of a non-empty map, pooled from F at the first request and kept; *built: this
+// call launched the pooling, bracketed by loc.ev[0] .. ev[1]
+int fmap_pooled(dpg_fmap* m, int shift, bool* built) {
+    if (shift <= 0 || m->cells() == 0 || m->have_pooled[shift]) return DPG_OK;
+    DpgLoc& L = m->loc;
+    const int32_t w = m->box[2], h = m->box[3], s = 1 << shift;
+    const int64_t pw = (int64_t)w + s - 1, ph = (int64_t)h + s - 1;
+    for (DevEvent& e : L.ev)
+        if (e.ensure(hipEventDefault)) return fail(DPG_ERR_HIP, "hipEventCreate failed");
+    if (L.pool_tmp.reserve((size_t)(pw * h)) || m->pooled[shift].reserve((size_t)(pw * ph)))
+        return fail(DPG_ERR_HIP, "out of device memory for a pooled field of %lld cells", (long long)(pw * ph));
+    HIP_TRY(hipEventRecord(L.ev[0].e, m->s));
+    loc_pool_kernel<true><<<blocks_for(pw * h), kT, 0, m->s>>>(m->field.p, L.pool_tmp.p, w, h, s);
+    HIP_TRY(hipGetLastError());
+    loc_pool_kernel<false><<<blocks_for(pw * ph), kT, 0, m->s>>>(L.pool_tmp.p, m->pooled[shift].p, (int32_t)pw, h, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(L.ev[1].e, m->s));
+    m->have_pooled[shift] = true;
+    *built = true;
+    return DPG_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+dpg_fmap* dpg_fmap_create(dpg_dpg* d, int64_t V, const float* est, const dpg_loc_params* p) {
+    const char* who = "dpg_fmap_create";
+    if (check_store(d, V, est, p, who)) return nullptr;
+    GridPlan gp;
+    double ms = 0.0;
+    if (plan_grid(d, V, est, *p, gp) || (gp.cells > 0 && build_field(d, gp, *p, 0, &ms))) return nullptr;
+    dpg_fmap* m = fmap_new(d->ctx, gp.box, gp.res, p->sigma, p->kernel_radius, p->occupied_min, who);
+    if (!m) return nullptr;
+    if (gp.cells > 0 && (hipMemcpyAsync(m->field.p, d->loc.field.p, (size_t)gp.cells, hipMemcpyDeviceToDevice, d->s) != hipSuccess ||
+                         hipStreamSynchronize(d->s) != hipSuccess)) {
+        dpg_fmap_destroy(m);
+        fail(DPG_ERR_HIP, "%s: the copy of the field failed", who);
+        return nullptr;
+    }
+    return m;
+}
+
+dpg_fmap* dpg_fmap_from_field(dpg_ctx* ctx, const uint8_t* F, const int32_t box[4], double res, float sigma,
+                              int32_t kernel_radius, int32_t occupied_min) {
+    const char* who = "dpg_fmap_from_field";
+    dpg_fmap* m = fmap_new(ctx, box, res, sigma, kernel_radius, occupied_min, who);
+    if (!m) return nullptr;
+    if (m->cells() > 0) {
+        if (!F) {
+            dpg_fmap_destroy(m);
+            fail(DPG_ERR_ARG, "%s: F is NULL", who);
+            return nullptr;
+        }
+        if (hipMemcpyAsync(m->field.p, F, (size_t)m->cells(), hipMemcpyHostToDevice, m->s) != hipSuccess ||
+            hipStreamSynchronize(m->s) != hipSuccess) {
+            dpg_fmap_destroy(m);
+            fail(DPG_ERR_HIP, "%s: the upload of the field failed", who);
+            return nullptr;
+        }
+    }
+    return m;
+}
+
+void dpg_fmap_destroy(dpg_fmap* m) {
+    if (!m) return;
+    dpg_ctx_release_child(m->ctx, m);
+    (void)hipSetDevice(m->device);
+    (void)hipStreamSynchronize(m->s);
+    delete m;
+}
+
+int dpg_fmap_info_get(const dpg_fmap* m, dpg_fmap_info* out) {
+    if (!m || !out) return fail(DPG_ERR_ARG, "dpg_fmap_info_get: a NULL argument");
+    memset(out, 0, sizeof(*out));
+    memcpy(out->box, m->box, sizeof(out->box));
+    out->res = m->res;
+    out->sigma = m->sigma;
+    out->kernel_radius = m->kernel_radius;
+    out->occupied_min = m->occupied_min;
+    out->n_bytes = m->cells();
+    return DPG_OK;
+}
+
+int dpg_fmap_fetch(dpg_fmap* m, uint8_t* out, int64_t cap) {
+    if (!m || (!out && m->cells() > 0)) return fail(DPG_ERR_ARG, "dpg_fmap_fetch: a NULL argument");
+    if (is_multi(m->ctx)) return fail(DPG_ERR_STATE, "dpg_fmap_fetch runs on a single-device context");
+    if (cap < m->cells()) return fail(DPG_ERR_SIZE, "dpg_fmap_fetch: out holds %lld bytes, the field has %lld", (long long)cap, (long long)m->cells());
+    if (m->cells() == 0) return DPG_OK;
+    HIP_TRY(hipSetDevice(m->device));
+    HIP_TRY(hipMemcpyAsync(out, m->field.p, (size_t)m->cells(), hipMemcpyDeviceToHost, m->s));
+    HIP_TRY(hipStreamSynchronize(m->s));
+    return DPG_OK;
+}
+
+int dpg_fmap_save(dpg_fmap* m, const char* path) {
+    if (!m || !path) return fail(DPG_ERR_ARG, "dpg_fmap_save: a NULL argument");
+    const int64_t n = m->cells();
+    std::vector<uint8_t> F((size_t)n);
+    int rc = dpg_fmap_fetch(m, F.data(), n);
+    if (rc) return rc;
+    unsigned char hdr[DPG_FMAP_HEADER_SIZE];
+    memset(hdr, 0, sizeof(hdr));
+    const uint32_t version = 1;
+    memcpy(hdr, "DPGFMAP1", 8);
+    memcpy(hdr + 8, &version, 4);
+    memcpy(hdr + 12, &m->kernel_radius, 4);
+    memcpy(hdr + 16, &m->occupied_min, 4);
+    memcpy(hdr + 20, &m->sigma, 4);
+    memcpy(hdr + 24, &m->res, 8);
+    memcpy(hdr + 32, m->box, 16);
+    memcpy(hdr + 48, &n, 8);
+    FILE* f = fopen(path, "wb");
+    if (!f) return fail(DPG_ERR_ARG, "dpg_fmap_save: cannot open %s for writing", path);
+    const bool ok = fwrite(hdr, 1, sizeof(hdr), f) == sizeof(hdr) && (n == 0 || fwrite(F.data(), 1, (size_t)n, f) == (size_t)n);
+    if (fclose(f) != 0 || !ok) return fail(DPG_ERR_ARG, "dpg_fmap_save: writing %s failed", path);
+    return DPG_OK;
+}
+
+dpg_fmap* dpg_fmap_load(dpg_ctx* ctx, const char* path) {
+    const char* who = "dpg_fmap_load";
+    if (!ctx || !path) { fail(DPG_ERR_ARG, "%s: a NULL argument", who); return nullptr; }
+    if (is_multi(ctx)) { fail(DPG_ERR_STATE, "%s: a frozen map lives on a single-device context", who); return nullptr; }
+    FILE* f = fopen(path, "rb");
+    if (!f) { fail(DPG_ERR_ARG, "%s: cannot open %s", who, path); return nullptr; }
+    unsigned char hdr[DPG_FMAP_HEADER_SIZE];
+    std::vector<uint8_t> F;
+    long size = -1;
+    bool ok = fseek(f, 0, SEEK_END) == 0 && (size = ftell(f)) >= (long)sizeof(hdr) && fseek(f, 0, SEEK_SET) == 0 &&
+              fread(hdr, 1, sizeof(hdr), f) == sizeof(hdr) && dpg_fmap_header_check(hdr, (int64_t)size) == DPG_OK;
+    if (ok) {
+        F.resize((size_t)size - sizeof(hdr));   // = w h <= 2^25, by the check
+        ok = F.empty() || fread(F.data(), 1, F.size(), f) == F.size();
+    }
+    fclose(f);
+    if (!ok) { fail(DPG_ERR_ARG, "%s: %s is not a frozen map file (magic, version, box, res, length or reserved bytes)", who, path); return nullptr; }
+    int32_t box[4], kernel_radius, occupied_min;
+    float sigma;
+    double res;
+    memcpy(&kernel_radius, hdr + 12, 4);
+    memcpy(&occupied_min, hdr + 16, 4);
+    memcpy(&sigma, hdr + 20, 4);
+    memcpy(&res, hdr + 24, 8);
+    memcpy(box, hdr + 32, 16);
+    return dpg_fmap_from_field(ctx, F.data(), box, res, sigma, kernel_radius, occupied_min);
+}
+
+int dpg_fmap_localize(dpg_fmap* m, const float* cloud, int64_t n_pts, const float guess[3], const dpg_loc_params* p,
+                      dpg_loc_result* result) {
+    const char* who = "dpg_fmap_localize";
+    if (!m || !p || !result) return fail(DPG_ERR_ARG, "%s: a NULL argument", who);
+    if (is_multi(m->ctx)) return fail(DPG_ERR_STATE, "%s runs on a single-device context", who);
+    // the fields that describe how a field is made are not read: the map has its own
+    dpg_loc_params P, D;
+    dpg_loc_params_default(&D);
+    P = *p;
+    P.resolution = D.resolution; P.max_cells = D.max_cells; P.margin_cells = D.margin_cells;
+    P.sigma = D.sigma; P.kernel_radius = D.kernel_radius; P.occupied_min = D.occupied_min;
+    if (dpg_loc_params_check(&P)) return fail(DPG_ERR_ARG, "%s: a parameter out of range", who);
+    int rc = check_request(cloud, n_pts, guess, P, kLocalize, 0, who);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(m->device));
+    View v;
+    if ((rc = fmap_pooled(m, P.coarse_shift, &v.built))) return rc;
+    v.F = m->field.p;
+    v.P = P.coarse_shift > 0 ? m->pooled[P.coarse_shift].p : m->field.p;
+    memcpy(v.box, m->box, sizeof(v.box));
+    v.res = m->res;
+    v.cells = m->cells();
+    v.L = &m->loc;
+    v.s = m->s;
+    return search(v, cloud, n_pts, guess, P, kLocalize, result, nullptr, who);
+}
 
 int dpg_map_localize(dpg_dpg* d, int64_t V, const float* est, const float* cloud, int64_t n_pts, const float guess[3],
                      const dpg_loc_params* p, dpg_loc_result* result) {

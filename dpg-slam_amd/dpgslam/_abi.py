@@ -297,6 +297,35 @@ DPG_LOC_NO_OVERLAP = 1
 DPG_LOC_UNPROVEN = 2
 
 
+class FmapInfo(C.Structure):
+    """dpg_fmap_info -- what a frozen map holds."""
+
+    _fields_ = [("box", C.c_int32 * 4), ("res", C.c_double), ("sigma", C.c_float), ("kernel_radius", C.c_int32),
+                ("occupied_min", C.c_int32), ("pad", C.c_int32), ("n_bytes", C.c_int64)]
+
+
+class TrackParams(C.Structure):
+    """dpg_track_params -- the window of dpg_fmap_track around each scan's guess."""
+
+    _fields_ = [("half_x", C.c_int32), ("half_y", C.c_int32), ("half_a", C.c_int32), ("angle_step", C.c_float)]
+
+
+class TrackResult(C.Structure):
+    """dpg_track_result -- the pose of one scan of a tracked batch."""
+
+    _fields_ = [("pose", C.c_float * 3), ("rot", C.c_float * 2), ("score", C.c_int32), ("score_at_guess", C.c_int32),
+                ("n_pts", C.c_int32), ("best_a", C.c_int32), ("best_dx", C.c_int32), ("best_dy", C.c_int32),
+                ("status", C.c_int32)]
+
+
+TRACK_RESULT_DTYPE = np.dtype(
+    [("pose", "<f4", (3,)), ("rot", "<f4", (2,)), ("score", "<i4"), ("score_at_guess", "<i4"), ("n_pts", "<i4"),
+     ("best_a", "<i4"), ("best_dx", "<i4"), ("best_dy", "<i4"), ("status", "<i4")], align=True)
+assert TRACK_RESULT_DTYPE.itemsize == C.sizeof(TrackResult) == 48 and C.sizeof(TrackParams) == 16
+assert C.sizeof(FmapInfo) == 48
+FMAP_HEADER_SIZE = 64
+
+
 ALLREDUCE_F64 = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int64)
 ALLREDUCE_F32 = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_float), C.c_int64)
 ALLGATHER = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
@@ -432,6 +461,19 @@ SIGNATURES = {
                                           C.c_int64]),
     "dpg_map_localize_scores": (C.c_int, [P, C.c_int64, F32P, F32P, C.c_int64, F32P, C.POINTER(LocParams), I32P,
                                           C.c_int64]),
+    "dpg_fmap_create": (P, [P, C.c_int64, F32P, C.POINTER(LocParams)]),
+    "dpg_fmap_from_field": (P, [P, U8P, I32P, C.c_double, C.c_float, C.c_int32, C.c_int32]),
+    "dpg_fmap_info_get": (C.c_int, [P, C.POINTER(FmapInfo)]),
+    "dpg_fmap_fetch": (C.c_int, [P, U8P, C.c_int64]),
+    "dpg_fmap_destroy": (None, [P]),
+    "dpg_fmap_save": (C.c_int, [P, C.c_char_p]),
+    "dpg_fmap_load": (P, [P, C.c_char_p]),
+    "dpg_fmap_header_check": (C.c_int, [C.c_void_p, C.c_int64]),
+    "dpg_fmap_localize": (C.c_int, [P, F32P, C.c_int64, F32P, C.POINTER(LocParams), C.POINTER(LocResult)]),
+    "dpg_track_params_default": (None, [C.POINTER(TrackParams)]),
+    "dpg_track_params_check": (C.c_int, [C.POINTER(TrackParams)]),
+    "dpg_fmap_track": (C.c_int, [P, F32P, I64P, C.c_int64, F32P, C.POINTER(TrackParams), P]),
+    "dpg_fmap_track_kernel_ms": (C.c_float, [P]),
     "dpg_reoptimize": (C.c_int, [P, C.c_int64, I32P, F32P, F32P, C.POINTER(IcpParams), C.POINTER(GnParams),
                                  C.POINTER(ReoptParams), F64P, C.POINTER(ReoptStats)]),
     "dpg_reoptimize_inc": (C.c_int, [P, C.c_int64, I32P, F32P, F32P, C.POINTER(IcpParams), C.POINTER(ReoptParams),
@@ -555,6 +597,12 @@ def default_csm_params() -> CsmParams:
 def default_loc_params() -> LocParams:
     p = LocParams()
     lib().dpg_loc_params_default(C.byref(p))
+    return p
+
+
+def default_track_params() -> TrackParams:
+    p = TrackParams()
+    lib().dpg_track_params_default(C.byref(p))
     return p
 
 

@@ -912,6 +912,14 @@ class DpgStore:
               "dpg_map_localize_scores")
         return out
 
+    def freeze(self, n_nodes: int, est, params=None) -> "FrozenMap":
+        """The likelihood field of the active map of nodes [0, n_nodes) at est, kept in a FrozenMap of its
+        own (dpg_fmap_create): later changes to this store, its closing included, do not reach it."""
+        e = _f32(est).reshape(-1, 3)
+        p = params or _abi.default_loc_params()
+        h = lib().dpg_fmap_create(self.handle, n_nodes, ptr(e, C.c_float), C.byref(p))
+        return FrozenMap(self.ctx, h, "dpg_fmap_create")
+
     def beam_geometry(self, n_nodes: int, est):
         """(lidar_xy [n_nodes, 2], end_xy [beams, 2]): each node's lidar position in the map and each
         beam's end point, as the device computes them (dpg_dpg_beam_geometry)."""
@@ -921,6 +929,108 @@ class DpgStore:
         check(lib().dpg_dpg_beam_geometry(self.handle, n_nodes, ptr(e, C.c_float), ptr(lidar, C.c_float),
                                           ptr(end, C.c_float), self.B), "dpg_dpg_beam_geometry")
         return lidar, end[:int(self.offsets[n_nodes])]
+
+
+class FrozenMap:
+    """A kept likelihood field (dpg_fmap): built once by DpgStore.freeze, from_field or load, then
+    searched (localize) and tracked against (track) without a rebuild.  It holds no reference to the
+    store it came from; a re-optimised graph needs a new freeze.  Lives on a single-device context."""
+
+    def __init__(self, ctx: Context, handle, what="dpg_fmap"):
+        if not handle:
+            raise _abi.DpgError(f"{what} failed: " + (lib().dpg_last_error() or b"").decode())
+        self.ctx = ctx
+        self.handle = handle
+        ctx._children.add(self)
+
+    @classmethod
+    def from_field(cls, ctx: Context, F, box, res, sigma=0.1, kernel_radius=3, occupied_min=50) -> "FrozenMap":
+        """F: uint8 [h, w] (any bytes); box = (x0, y0, w, h); the last three only describe how F was made."""
+        b = np.ascontiguousarray(box, np.int32).reshape(4)
+        f = np.ascontiguousarray(F, np.uint8)
+        if f.size != max(int(b[2]), 0) * max(int(b[3]), 0):
+            raise ValueError(f"from_field: F has {f.size} bytes, the box {int(b[2])} x {int(b[3])} cells")
+        h = lib().dpg_fmap_from_field(ctx.handle, ptr(f.reshape(-1), C.c_uint8), ptr(b, C.c_int32), float(res), float(sigma),
+                                      int(kernel_radius), int(occupied_min))
+        return cls(ctx, h, "dpg_fmap_from_field")
+
+    @classmethod
+    def load(cls, ctx: Context, path) -> "FrozenMap":
+        return cls(ctx, lib().dpg_fmap_load(ctx.handle, os.fsencode(path)), "dpg_fmap_load")
+
+    def close(self):
+        if getattr(self, "handle", None):
+            if _ctx_gone(self):   # finalized after its context: dpg_ctx_destroy already destroyed it
+                self.handle = None
+                return
+            lib().dpg_fmap_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self) -> dict:
+        """dict of `box` (x0, y0, w, h), `res`, `sigma`, `kernel_radius`, `occupied_min`, `n_bytes`."""
+        i = _abi.FmapInfo()
+        check(lib().dpg_fmap_info_get(self.handle, C.byref(i)), "dpg_fmap_info_get")
+        return dict(box=tuple(int(b) for b in i.box), res=float(i.res), sigma=float(i.sigma),
+                    kernel_radius=int(i.kernel_radius), occupied_min=int(i.occupied_min), n_bytes=int(i.n_bytes))
+
+    def field(self) -> np.ndarray:
+        """F, uint8 [h, w] ((0, 0) for an empty map)."""
+        _, _, w, h = self.info()["box"]
+        out = np.zeros((h, w) if w * h else (0, 0), np.uint8)
+        check(lib().dpg_fmap_fetch(self.handle, ptr(out, C.c_uint8), out.size), "dpg_fmap_fetch")
+        return out
+
+    def save(self, path):
+        check(lib().dpg_fmap_save(self.handle, os.fsencode(path)), "dpg_fmap_save")
+
+    def localize(self, cloud, guess=(0.0, 0.0, 0.0), params=None, window=None):
+        """DpgStore.localize on this map (dpg_fmap_localize): a LOC_RESULT_DTYPE record.  window="map"
+        centres the translation window on the box and makes it cover the box."""
+        c = _f32(cloud).reshape(-1, 2)
+        g = _f32(guess).reshape(3)
+        p = params or _abi.default_loc_params()
+        if window == "map":
+            i = self.info()
+            x0, y0, w, h = i["box"]
+            q = _abi.LocParams.from_buffer_copy(bytes(p))
+            q.half_x, q.half_y = min(w // 2 + 1, 32768), min(h // 2 + 1, 32768)
+            g = _f32([(x0 + w // 2) * i["res"], (y0 + h // 2) * i["res"], g[2]])
+            p = q
+        elif window is not None:
+            raise ValueError(f"localize: window must be None or 'map', got {window!r}")
+        r = _abi.LocResult()
+        check(lib().dpg_fmap_localize(self.handle, ptr(c, C.c_float), len(c), ptr(g, C.c_float), C.byref(p), C.byref(r)),
+              "dpg_fmap_localize")
+        return np.frombuffer(bytes(r), _abi.LOC_RESULT_DTYPE)[0].copy()
+
+    def track(self, clouds, guesses, params=None, offsets=None) -> np.ndarray:
+        """A batch of scans, each searched exhaustively over the params' window around its own guess
+        (dpg_fmap_track): TRACK_RESULT_DTYPE records [B].  clouds: a list of [n_b, 2] arrays, or one
+        [N, 2] array with offsets [B + 1]; guesses [B, 3]."""
+        if offsets is None:
+            cl = [_f32(c).reshape(-1, 2) for c in clouds]
+            off = np.zeros(len(cl) + 1, np.int64)
+            off[1:] = np.cumsum([len(c) for c in cl])
+            pts = np.concatenate(cl) if cl else np.zeros((0, 2), np.float32)
+        else:
+            pts = _f32(clouds).reshape(-1, 2)
+            off = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+        pts = np.ascontiguousarray(pts, np.float32)
+        B = len(off) - 1
+        g = _f32(guesses).reshape(-1, 3)
+        if len(g) != B:
+            raise ValueError(f"track: {B} scans and {len(g)} guesses")
+        p = params or _abi.default_track_params()
+        out = np.zeros(B, _abi.TRACK_RESULT_DTYPE)
+        check(lib().dpg_fmap_track(self.handle, ptr(pts, C.c_float), ptr(off, C.c_int64), B, ptr(g, C.c_float), C.byref(p),
+                                   _abi.vptr(out)), "dpg_fmap_track")
+        return out
 
 
 class IncGraph:

@@ -178,6 +178,8 @@ class DpgSLAM:
         self._store = None
         self._store_V = 0
         self.last_dpg = None                            # dpg_change_stats of the last executeDPG
+        self._loc = None                                # localisation-only mode's state (StartLocalization)
+        self.last_track = None                          # the record of the last tracked scan
 
     # ------------------------------------------------------------------ public API
     def ObserveOdometry(self, odom_loc, odom_angle):
@@ -190,6 +192,9 @@ class DpgSLAM:
 
     def ObserveLaser(self, ranges, range_min, range_max, angle_min, angle_max):
         """dpg_slam.cc:122-140."""
+        if self._loc is not None:   # localisation-only mode: track, create nothing
+            self._track_laser(np.asarray(ranges, f32), f32(range_max), f32(angle_min), f32(angle_max))
+            return
         if not self.odom_initialized:
             return
         if not self._update_pose_graph(np.asarray(ranges, f32), f32(range_max), f32(angle_min), f32(angle_max)):
@@ -207,13 +212,102 @@ class DpgSLAM:
 
     def GetPose(self):
         """dpg_slam.cc:528-553: the last node's estimate plus the odometry not yet in the graph."""
+        if self._loc is not None:   # localisation-only mode: the tracked pose plus the odometry since that track
+            return self._tracked_pose()
         loc = self.poses[-1][:2] if len(self.poses) else np.zeros(2, f32)
         ang = self.poses[-1][2] if len(self.poses) else f32(0)
-        un = self.prev_odom[:2] - self.odom_at_last_align[:2]
-        dth = _angle_mod(self.prev_odom[2] - self.odom_at_last_align[2])   # AngleDiff
-        disp = api.transform_point(np.array([un[0], un[1], 0], f32), np.array([0, 0, -self.odom_at_last_align[2]], f32))
+        return self._plus_odometry(loc, ang, self.odom_at_last_align)
+
+    def _plus_odometry(self, loc, ang, odom_ref):
+        """(loc, ang) moved by the odometry since odom_ref, as GetPose composes it (dpg_slam.cc:528-553)."""
+        un = self.prev_odom[:2] - odom_ref[:2]
+        dth = _angle_mod(self.prev_odom[2] - odom_ref[2])   # AngleDiff
+        disp = api.transform_point(np.array([un[0], un[1], 0], f32), np.array([0, 0, -odom_ref[2]], f32))
         rot = api.transform_point(np.array([disp[0], disp[1], 0], f32), np.array([0, 0, ang], f32))
         return np.array([loc[0] + rot[0], loc[1] + rot[1]], f32), f32(ang + dth)
+
+    # ------------------------------------------------------------------ localisation-only mode
+    def StartLocalization(self, track_params=None, loc_params=None, fmap=None, pose=None, min_response=0.0,
+                          icp_refine=True):
+        """Localisation-only mode: from here to StopLocalization every ObserveLaser tracks its scan in a
+        frozen map (dpg_fmap_track over track_params' window) and creates no node and no factor; the
+        store and the graph are not touched.  fmap None: the current active map is frozen
+        (store.freeze(V, poses, loc_params)); else an api.FrozenMap, e.g. a loaded one.  The tracked
+        pose starts at `pose` (x, y, theta), or at GetPose() when None.
+        Per scan: guess = the tracked pose composed with the odometry since it was set (GetPose's
+        arithmetic); r = fmap.track([cloud], [guess])[0], kept in last_track.  With status DPG_LOC_OK
+        and score / (255 n_pts) >= min_response the tracked pose becomes r.pose -- or, with icp_refine,
+        the pose of one run_icp of the scan at r.pose against the nearest node that was active at the
+        freeze, when that ICP converges.  Otherwise it is left alone and dead-reckons on."""
+        if pose is None and not len(self.poses):
+            raise ValueError("StartLocalization: the graph has no node yet and no pose was given")
+        V = len(self.poses)
+        store = self._dpg_store() if V else None
+        if fmap is None:
+            fn = getattr(store, "freeze", None)
+            if fn is None:
+                raise NotImplementedError(f"StartLocalization needs a `freeze(n_nodes, est, params)` method on the backend's "
+                                          f"node store; {type(store).__name__} has none")
+            fmap, own = fn(V, self.poses, loc_params), True
+        else:
+            own = False
+        if getattr(fmap, "track", None) is None:
+            raise NotImplementedError(f"StartLocalization needs a `track(clouds, guesses, params)` method on the map; "
+                                      f"{type(fmap).__name__} has none")
+        icp = None
+        if icp_refine:
+            icp = getattr(getattr(self.be, "ctx", None), "run_icp", None)
+            if icp is None:
+                raise NotImplementedError(f"StartLocalization(icp_refine=True) needs a `ctx.run_icp` on the backend; "
+                                          f"{type(self.be).__name__} has none")
+        nodes = np.arange(V)
+        fetch = getattr(store, "fetch", None)
+        if V and fetch is not None:
+            nodes = np.nonzero(np.asarray(fetch()[2][:V]))[0]
+        if pose is None:
+            loc, ang = self.GetPose()
+            pose = (loc[0], loc[1], ang)
+        self.last_track = None
+        self._loc = dict(fmap=fmap, own=own, params=track_params, min_response=float(min_response), icp=icp,
+                         nodes=nodes, node_poses=self.poses[nodes].copy(), pose=np.asarray(pose, f32).reshape(3).copy(),
+                         odom_ref=self.prev_odom.copy() if self.odom_initialized else None)
+
+    def StopLocalization(self):
+        """Leaves the mode and changes nothing else: mapping continues as if the scans delivered in
+        between had never arrived.  A map frozen by StartLocalization is closed."""
+        if self._loc is not None and self._loc["own"]:
+            self._loc["fmap"].close()
+        self._loc = None
+
+    def _tracked_pose(self):
+        """The tracked pose plus the odometry since it was set."""
+        m = self._loc
+        if m["odom_ref"] is None:   # no odometry yet: nothing to add
+            return m["pose"][:2].copy(), f32(m["pose"][2])
+        return self._plus_odometry(m["pose"][:2], m["pose"][2], m["odom_ref"])
+
+    def _track_laser(self, ranges, range_max, angle_min, angle_max):
+        m = self._loc
+        if m["odom_ref"] is None and self.odom_initialized:
+            m["odom_ref"] = self.prev_odom.copy()
+        cloud = api.scan_to_cloud(ranges, angle_min, angle_max, range_max, self.laser)
+        loc, ang = self._tracked_pose()
+        guess = np.array([loc[0], loc[1], ang], f32)
+        r = m["fmap"].track([cloud], [guess], m["params"])[0]
+        self.last_track = r
+        response = float(r["score"]) / (255.0 * max(int(r["n_pts"]), 1))
+        if int(r["status"]) != _abi.DPG_LOC_OK or response < m["min_response"]:
+            return                                  # the tracked pose dead-reckons on
+        pose = np.array(r["pose"], f32)
+        if m["icp"] is not None and len(m["nodes"]):
+            d = m["node_poses"][:, :2].astype(np.float64) - pose[:2].astype(np.float64)
+            k = int(np.argmin(d[:, 0] ** 2 + d[:, 1] ** 2))
+            t = int(m["nodes"][k])
+            ok, z, *_ = m["icp"](api.Node(m["node_poses"][k], self.clouds[t]), api.Node(pose, cloud), self.icp_params)
+            if ok:
+                pose = api.transform_point(np.array([z[0][0], z[0][1], z[1]], f32), m["node_poses"][k])
+        m["pose"] = pose
+        m["odom_ref"] = self.prev_odom.copy() if self.odom_initialized else None
 
     def GetPoseCovariance(self, node=None):
         """The 3x3 marginal covariance of a node's pose (default: the latest node), in the pose's own

@@ -971,7 +971,7 @@ int dpg_icp_batch_prepare_guess(dpg_ctx* ctx, const int32_t* edges, int64_t n_ed
  *   Sizes: n_pts <= 2^23 (255 n_pts fits int32); (2 half_a + 1) nbx nby and (2 half_a + 1) n_pts at
  *     most 2^29 each (DPG_ERR_SIZE beyond: the bound volume and the key table are device arrays), and
  *     min(max_refine_blocks, blocks) s^2 at most 2^36 (one launch scores the frontier).
- * The field is rebuilt by every call.  The call reads the store as dpg_occupancy_grid does and writes
+ * The field is rebuilt by every call (a dpg_fmap, below, keeps one).  The call reads the store as dpg_occupancy_grid does and writes
  * nothing of executeDPG's state or of the grid's outputs; F, P and the search buffers belong to the
  * store, allocated at first use and regrown only for a larger request. */
 typedef struct dpg_loc_params {
@@ -1043,6 +1043,103 @@ int dpg_map_localize_bounds(dpg_dpg* d, int64_t n_nodes, const float* est_poses,
  * kernel run over every block */
 int dpg_map_localize_scores(dpg_dpg* d, int64_t n_nodes, const float* est_poses, const float* cloud_xy, int64_t n_pts,
                             const float guess[3], const dpg_loc_params* params, int32_t* out, int64_t cap);
+
+/* ---- frozen map: a kept likelihood field that scans are localised and tracked against ----
+ * dpg_map_localize rebuilds grid and field on every call.  A dpg_fmap holds F, its box and its
+ * resolution in buffers of its own: it is built (or loaded) once, searched any number of times, and
+ * keeps no reference to the store it was taken from -- the store may be appended to, relabelled or
+ * destroyed afterwards and the map does not change.  "Frozen" means exactly that: a re-optimised
+ * graph, or a map whose nodes changed, needs a new freeze.  A map is a child of its context
+ * (dpg_ctx_destroy destroys it), runs on the context's stream and exists on single-device contexts
+ * only: the creators return NULL (dpg_last_error) on a multi-device, virtual or rank context, the
+ * other calls DPG_ERR_STATE.  The reference has no such stage.
+ *
+ * dpg_fmap_create: the grid and the field exactly as dpg_map_localize makes them for (d, n_nodes,
+ *   est_poses, params) -- box, res and the bytes of dpg_map_field(shift < 0) -- copied into the
+ *   handle.  Of params only resolution, max_cells, margin_cells, sigma, kernel_radius and occupied_min
+ *   matter (all of it is checked).  No active node gives an empty map (w = h = 0): valid, and every
+ *   search on it answers DPG_LOC_NO_OVERLAP.
+ * dpg_fmap_from_field: F [h][w] as given (any bytes), box = (x0, y0, w, h); sigma, kernel_radius and
+ *   occupied_min only describe how F was made.  DPG_ERR_ARG (NULL): res not finite or <= 0, w or
+ *   h < 0, w h above 2^25, F NULL with w h > 0.
+ * File (dpg_fmap_save / _load), little-endian: a 64-byte header, then F row-major.
+ *     0 magic "DPGFMAP1" | 8 uint32 version = 1 | 12 int32 kernel_radius | 16 int32 occupied_min |
+ *    20 float sigma | 24 double res | 32 int32 box[4] | 48 int64 n_bytes = w h | 56 eight zero bytes
+ *   dpg_fmap_header_check (host, plain C): DPG_OK, or DPG_ERR_ARG for a wrong magic or version, a
+ *   bad box or res (as dpg_fmap_from_field), n_bytes != w h, file_bytes != 64 + n_bytes, or a
+ *   non-zero reserved byte.  dpg_fmap_load returns NULL for such a file or one it cannot read. */
+typedef struct dpg_fmap dpg_fmap;
+typedef struct dpg_fmap_info {
+    int32_t box[4];             /* x0, y0, w, h */
+    double res;
+    float sigma;
+    int32_t kernel_radius, occupied_min;
+    int32_t pad;
+    int64_t n_bytes;            /* w h: the bytes of F held */
+} dpg_fmap_info;
+#define DPG_FMAP_INFO_SIZE 48
+#define DPG_FMAP_HEADER_SIZE 64
+
+dpg_fmap* dpg_fmap_create(dpg_dpg* d, int64_t n_nodes, const float* est_poses, const dpg_loc_params* params);
+dpg_fmap* dpg_fmap_from_field(dpg_ctx* ctx, const uint8_t* F, const int32_t box[4], double res, float sigma,
+                              int32_t kernel_radius, int32_t occupied_min);
+int dpg_fmap_info_get(const dpg_fmap* m, dpg_fmap_info* out);
+/* out[h][w] = F; cap in bytes, DPG_ERR_SIZE with nothing written when too small */
+int dpg_fmap_fetch(dpg_fmap* m, uint8_t* out, int64_t cap);
+void dpg_fmap_destroy(dpg_fmap* m);
+int dpg_fmap_save(dpg_fmap* m, const char* path);
+dpg_fmap* dpg_fmap_load(dpg_ctx* ctx, const char* path);
+int dpg_fmap_header_check(const void* hdr64, int64_t file_bytes);
+/* dpg_map_localize's contract word for word, with F, the box and res taken from the map.  Of params,
+ * resolution, max_cells, margin_cells, sigma, kernel_radius and occupied_min are NOT read (nor
+ * checked).  P for a coarse_shift is pooled from the map's F at the first request for that shift and
+ * kept.  ms_field is 0 when the call built nothing (it covers the pooling when it did).  Errors:
+ * DPG_ERR_ARG, DPG_ERR_SIZE as dpg_map_localize for the request; DPG_ERR_STATE as above. */
+int dpg_fmap_localize(dpg_fmap* m, const float* cloud_xy, int64_t n_pts, const float guess[3],
+                      const dpg_loc_params* params, dpg_loc_result* result);
+
+/* dpg_fmap_track: a batch of scans, each searched EXHAUSTIVELY over a small window around its own
+ * guess, in one enqueue.  Scan b is clouds_xy[offsets[b] .. offsets[b + 1]); its record is that of
+ * dpg_loc_params / dpg_loc_result for the same half_x, half_y, half_a, angle_step and guess at
+ * coarse_shift 0: rotations (dpg_loc_rotations' rule), keys, score, the winner and its tie order,
+ * pose, rot and score_at_guess.  status: DPG_LOC_NO_OVERLAP when the winner's score is 0, else
+ * DPG_LOC_OK.  After the one float transform per point and angle everything is integer: outputs are
+ * exact and two calls give the same bytes.  One upload, the launches, one copy back and one
+ * synchronisation per call, whatever B is; B = 0 and an empty map launch nothing.
+ * Errors, all before anything is launched or written: DPG_ERR_ARG -- NULL arguments, params out of
+ * range, B < 0, offsets[0] < 0 or offsets not monotone, a guess whose x or y has no valid key or whose
+ * angle is not finite; DPG_ERR_SIZE -- B above 65535, a scan above 2^23 points, more than 2^26
+ * points in all; DPG_ERR_STATE as above. */
+typedef struct dpg_track_params {
+    int32_t half_x, half_y;     /* translation window, cells, default 10, 10; 0 .. 64 */
+    int32_t half_a;             /* angle window, steps, default 10; 0 .. 64 */
+    float angle_step;           /* radians per step, default 0.5 degrees; finite, > 0 */
+} dpg_track_params;
+typedef struct dpg_track_result {
+    float pose[3];              /* x, y, theta in the map's frame */
+    float rot[2];               /* (c_a, s_a) of the winner */
+    int32_t score;
+    int32_t score_at_guess;     /* score(half_a, 0, 0) */
+    int32_t n_pts;              /* the scan's points: the largest possible score is 255 n_pts */
+    int32_t best_a, best_dx, best_dy;
+    int32_t status;             /* DPG_LOC_OK or DPG_LOC_NO_OVERLAP */
+} dpg_track_result;
+#define DPG_TRACK_PARAMS_SIZE 16
+#define DPG_TRACK_RESULT_SIZE 48
+#ifdef __cplusplus
+ static_assert(sizeof(dpg_track_params) == DPG_TRACK_PARAMS_SIZE && sizeof(dpg_track_result) == DPG_TRACK_RESULT_SIZE &&
+               sizeof(dpg_fmap_info) == DPG_FMAP_INFO_SIZE, "track ABI structs");
+#else
+ _Static_assert(sizeof(dpg_track_params) == DPG_TRACK_PARAMS_SIZE && sizeof(dpg_track_result) == DPG_TRACK_RESULT_SIZE &&
+                sizeof(dpg_fmap_info) == DPG_FMAP_INFO_SIZE, "track ABI structs");
+#endif
+void dpg_track_params_default(dpg_track_params* p);
+/* Host.  DPG_OK or DPG_ERR_ARG: every field against the ranges above. */
+int dpg_track_params_check(const dpg_track_params* p);
+int dpg_fmap_track(dpg_fmap* m, const float* clouds_xy, const int64_t* offsets, int64_t B, const float* guesses,
+                   const dpg_track_params* params, dpg_track_result* out);
+/* ms of the two launches of the last dpg_fmap_track that launched anything (HIP events) */
+float dpg_fmap_track_kernel_ms(const dpg_fmap* m);
 
 #ifdef __cplusplus
 }
