@@ -4,7 +4,7 @@
 // store, batched and single ICP, covariance), dpg_gn_api.hip (pose graph, marginals) and
 // dpg_sweep.hip (re-linearisation sweep, dpg_add_node); the few functions they call across each
 // other are declared at the end.  The DPG store has a header of its own, dpg_dpg.h (dpg_store.hip, dpg_change.hip,
-// dpg_grid.hip, dpg_loc.hip, dpg_track.hip; dpg_raster.h, dpg_loc_dev.h, dpg_change_plan.cpp).  Nothing here is exported from the library.
+// dpg_grid.hip, dpg_loc.hip, dpg_track.hip, dpg_refine.hip; dpg_raster.h, dpg_loc_dev.h, dpg_change_plan.cpp).  Nothing here is exported from the library.
 // Every device array, pinned or host-mapped block, event, stream and solver handle of the layer is a
 // member that releases itself (DevBuf / PinBuf / MappedBuf, DevEvent, DevStream, CholPtr) of the
 // context, its batch graph (GnGraph), its collective thread (HostColl) or a child: the release calls

@@ -1,5 +1,5 @@
 // dpg_dpg.h -- the DPG node store (struct dpg_dpg) as dpg_store.hip, dpg_change.hip, dpg_grid.hip and
-// dpg_loc.hip see it, and the frozen map (struct dpg_fmap) of dpg_loc.hip and dpg_track.hip (private,
+// dpg_loc.hip see it, and the frozen map (struct dpg_fmap) of dpg_loc.hip, dpg_track.hip and dpg_refine.hip (private,
 // C++).  Every array releases itself; kernels take the view DS (make_ds).
 #ifndef DPG_DPG_H
 #define DPG_DPG_H
@@ -111,7 +111,8 @@ struct dpg_dpg {
 
 // A frozen map (dpg_fmap_*): a likelihood field with its box and resolution in buffers of its own, a
 // child of the context that keeps no reference to the store it was taken from.  dpg_loc.hip creates,
-// saves, loads and searches it; dpg_track.hip tracks batches of scans against it.
+// saves, loads and searches it; dpg_track.hip tracks batches of scans against it, dpg_refine.hip
+// refines their poses on it.
 struct TrackRec { LocRec win; int32_t score_at_guess, pad[3]; };   // a scan's record as the device leaves it
 struct dpg_fmap {
     dpg_ctx* ctx = nullptr;
@@ -135,8 +136,38 @@ struct dpg_fmap {
     PinBuf<TrackRec> h_recs;
     DevEvent track_ev[2];                     // around the two launches of the last call
     float track_ms = 0.f;
+    // dpg_fmap_refine / dpg_fmap_track_refine (dpg_refine.hip): the call's one block of results on the
+    // device and pinned -- [the track records |] the refine records [| the trace]; the upload goes
+    // through h_in and d_in
+    DevBuf<unsigned char> r_out;
+    PinBuf<unsigned char> h_rout;
+    DevEvent refine_ev[2];                    // around the refinement launch of the last call
+    float refine_ms = 0.f;
     int64_t cells() const { return (int64_t)box[2] * box[3]; }
 };
+
+// ---- dpg_track.hip: dpg_fmap_track in the stages that dpg_fmap_track_refine (dpg_refine.hip) shares ----
+// one scan of the batch as the kernels read it: its points [begin, end) of the batch's cloud array and
+// the keys (cx, cy) of its guess
+struct TrackScan { int64_t begin, end; int32_t cx, cy, pad[2]; };
+// a checked request staged in m->h_in, one block: scans [B] | rot [B][A][2] | the points from offsets[0] on
+struct TrackStage {
+    dpg_track_params P;
+    int64_t B = 0, A = 0, total = 0;
+    size_t o_scan = 0, o_rot = 0, o_pts = 0, n_in = 0;
+    TrackScan* scans = nullptr;               // in m->h_in
+    float* rot = nullptr;
+};
+// every check of dpg_fmap_track's contract, nothing touched; B = 0 passes
+int track_check(dpg_fmap* m, const float* clouds, const int64_t* offsets, int64_t B, const float* guesses,
+                const dpg_track_params* p, const void* out, const char* who);
+// B > 0, checked: makes the map's device current, waits for its stream and fills h_in
+int track_stage(dpg_fmap* m, const float* clouds, const int64_t* offsets, int64_t B, const float* guesses,
+                const dpg_track_params* p, const char* who, TrackStage& st);
+// a map with cells: the two launches over the block uploaded at d_in, the records to d_recs [B]
+int track_launch(dpg_fmap* m, const TrackStage& st, TrackRec* d_recs, const char* who);
+// out[B] from the device's records (recs NULL: an empty map's)
+void track_results(const dpg_fmap* m, const TrackStage& st, const float* guesses, const TrackRec* recs, dpg_track_result* out);
 
 // ---- dpg_store.hip ----
 DS make_ds(dpg_dpg* d);

@@ -270,6 +270,111 @@ int dpg_track_params_check(const dpg_track_params* p) {
     return DPG_OK;
 }
 
+/* ---- dpg_fmap_refine: parameters, starts and the record (the contract is above dpg_refine_params in
+ * include/dpg_slam_c.h; every expression stands as written there) ---- */
+void dpg_refine_params_default(dpg_refine_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->max_iters = 20;
+    p->lambda = 1e-3;
+    p->max_step_cells = 1.0;
+    p->max_step_angle = 0.02;
+    p->tol_cells = 1e-3;
+    p->tol_angle = 1e-5;
+}
+
+int dpg_refine_params_check(const dpg_refine_params* p) {
+    if (!p) return DPG_ERR_ARG;
+    if (p->max_iters < 0 || p->max_iters > 64) return DPG_ERR_ARG;
+    if (!(p->lambda >= 0.0) || !isfinite(p->lambda)) return DPG_ERR_ARG;
+    if (!(p->max_step_cells > 0.0) || !isfinite(p->max_step_cells) || !(p->max_step_angle > 0.0) || !isfinite(p->max_step_angle))
+        return DPG_ERR_ARG;
+    if (!(p->tol_cells >= 0.0) || !isfinite(p->tol_cells) || !(p->tol_angle >= 0.0) || !isfinite(p->tol_angle)) return DPG_ERR_ARG;
+    return DPG_OK;
+}
+
+int dpg_refine_start(const float pose[3], float out[5]) {
+    if (!pose || !out) return DPG_ERR_ARG;
+    out[0] = pose[0];
+    out[1] = pose[1];
+    out[2] = pose[2];
+    out[3] = (float)cos((double)pose[2]);
+    out[4] = (float)sin((double)pose[2]);
+    return DPG_OK;
+}
+
+float dpg_refine_angle(double c, double s) { return (float)atan2(s, c); }
+
+int dpg_refine_start_check(const float start[5], double ires) {
+    const double c = (double)start[3], s = (double)start[4];
+    if (!isfinite(start[0]) || !isfinite(start[1]) || !isfinite(start[3]) || !isfinite(start[4])) return DPG_ERR_ARG;
+    if (!(fabs((double)start[0] * ires) < 536870912.0) || !(fabs((double)start[1] * ires) < 536870912.0)) return DPG_ERR_ARG;
+    const double n2 = (c * c) + (s * s);
+    if (!(n2 >= 0.5 && n2 <= 2.0)) return DPG_ERR_ARG;
+    return DPG_OK;
+}
+
+/* the step's solve: H = (H00 H01 H02 H11 H12 H22), z = (H + lambda diag H)^-1 b; 0 for a failed pivot */
+static int refine_solve(const double H[6], double lambda, const double b[3], double z[3]) {
+    const double eps = 1e-12;
+    const double D1 = H[3] + (lambda * H[3]), D2 = H[5] + (lambda * H[5]);
+    const double d0 = H[0] + (lambda * H[0]);
+    if (!(d0 > 0.0)) return 0;
+    const double l10 = H[1] / d0, l20 = H[2] / d0;
+    const double d1 = D1 - (l10 * H[1]);
+    if (!(d1 > eps * D1)) return 0;
+    const double e12 = H[4] - (l20 * H[1]), l21 = e12 / d1;
+    const double d2 = (D2 - (l20 * H[2])) - (l21 * e12);
+    if (!(d2 > eps * D2)) return 0;
+    const double y0 = b[0], y1 = b[1] - (l10 * y0), y2 = (b[2] - (l20 * y0)) - (l21 * y1);
+    z[2] = y2 / d2;
+    z[1] = (y1 / d1) - (l21 * z[2]);
+    z[0] = ((y0 / d0) - (l10 * z[1])) - (l20 * z[2]);
+    return 1;
+}
+
+void dpg_refine_record(int32_t status, int32_t n_evals, int32_t best_eval, int32_t n_used, const double state[4],
+                       const double S[11], double cost_start, const int32_t box[4], double res, dpg_refine_result* out) {
+    dpg_refine_result r;
+    memset(&r, 0, sizeof(r));
+    r.pose[0] = (float)((state[0] + (double)box[0]) * res);
+    r.pose[1] = (float)((state[1] + (double)box[1]) * res);
+    r.pose[2] = dpg_refine_angle(state[2], state[3]);
+    r.rot[0] = (float)state[2];
+    r.rot[1] = (float)state[3];
+    r.status = status;
+    r.n_evals = n_evals;
+    r.best_eval = best_eval;
+    r.n_used = n_used;
+    r.tu = state[0]; r.tv = state[1]; r.c = state[2]; r.s = state[3];
+    r.cost = S[9];
+    r.cost_start = cost_start;
+    r.sum_r = S[10];
+    for (int i = 0; i < 6; ++i) r.hess[i] = S[i];
+    /* cov = s2 H^-1: column j from the unit vector e_j, entry (i, j), i <= j, from column j */
+    const double s2 = S[9] / (double)(n_used - 3 > 1 ? n_used - 3 : 1);
+    double col[3][3];
+    int ok = 1;
+    for (int j = 0; j < 3 && ok; ++j) {
+        const double e[3] = {j == 0 ? 1.0 : 0.0, j == 1 ? 1.0 : 0.0, j == 2 ? 1.0 : 0.0};
+        ok = refine_solve(S, 0.0, e, col[j]);
+    }
+    if (ok) {
+        const double rr = res * res;
+        r.cov[0] = (s2 * col[0][0]) * rr;
+        r.cov[1] = (s2 * col[1][0]) * rr;
+        r.cov[2] = (s2 * col[2][0]) * res;
+        r.cov[3] = (s2 * col[1][1]) * rr;
+        r.cov[4] = (s2 * col[2][1]) * res;
+        r.cov[5] = s2 * col[2][2];
+        for (int i = 0; i < 6; ++i)
+            if (!isfinite(r.cov[i])) ok = 0;
+        if (!ok) memset(r.cov, 0, sizeof(r.cov));
+    }
+    r.cov_ok = ok;
+    *out = r;
+}
+
 /* the frozen map's file header (the layout is in dpg_slam_c.h); the host is little-endian */
 int dpg_fmap_header_check(const void* hdr64, int64_t file_bytes) {
     if (!hdr64) return DPG_ERR_ARG;

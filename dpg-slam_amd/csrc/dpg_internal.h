@@ -269,6 +269,14 @@ int dpg_gn_dev_assemble_part(dpg_gn_dev* g, const int32_t* gate, void* stream);
 /* virtual devices: outs[r] = sum over q in rank order of parts[q], n doubles, r < k <= 16 */
 int dpg_launch_vsum(const double* const* parts, double* const* outs, int32_t k, int64_t n, void* stream);
 
+/* dpg_fmap_refine (dpg_host.c): the host's part of the contract above dpg_refine_params.
+   dpg_refine_start_check: DPG_OK or DPG_ERR_ARG for a start (x, y, theta, c, s) against ires = 1.0 / res.
+   dpg_refine_record: the record of a scan from what the device left: status, n_evals, best_eval,
+   n_used, the best iterate's state (tu, tv, c, s), its sums S[11] and the cost of evaluation 0. */
+int dpg_refine_start_check(const float start[5], double ires);
+void dpg_refine_record(int32_t status, int32_t n_evals, int32_t best_eval, int32_t n_used, const double state[4],
+                       const double S[11], double cost_start, const int32_t box[4], double res, dpg_refine_result* out);
+
 #ifdef __cplusplus
 }
 #endif

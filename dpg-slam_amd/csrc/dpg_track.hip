@@ -16,6 +16,8 @@
 //   track_reduce_kernel  a workgroup per scan: the best of its angles
 // Every loop is bounded by the validated parameters and the offsets, every index is tested against
 // the box at its access, no workgroup waits for another and no result goes through an atomic.
+// The host side is in stages (track_check, track_stage, track_launch, track_results: dpg_dpg.h) that
+// dpg_fmap_track_refine (dpg_refine.hip) runs too, with its refinement enqueued behind the launches.
 
 #include <math.h>
 #include <string.h>
@@ -33,10 +35,6 @@ struct TrackDims {
     int32_t A, wx, n_shifts;   // 2 ha + 1, 2 hx + 1, (2 hx + 1)(2 hy + 1)
     double res;
 };
-
-// one scan of the batch as the kernels read it: its points [begin, end) of the batch's cloud array and
-// the keys (cx, cy) of its guess
-struct TrackScan { int64_t begin, end; int32_t cx, cy, pad[2]; };
 
 // grid (A, B)
 __global__ __launch_bounds__(kLocT) void track_scan_kernel(TrackDims g, const TrackScan* scans, const float2* cloud, const float* rot,
@@ -120,11 +118,8 @@ size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 }  // namespace
 
-extern "C" float dpg_fmap_track_kernel_ms(const dpg_fmap* m) { return m ? m->track_ms : 0.f; }
-
-extern "C" int dpg_fmap_track(dpg_fmap* m, const float* clouds, const int64_t* offsets, int64_t B, const float* guesses,
-                              const dpg_track_params* p, dpg_track_result* out) {
-    const char* who = "dpg_fmap_track";
+int track_check(dpg_fmap* m, const float* clouds, const int64_t* offsets, int64_t B, const float* guesses,
+                const dpg_track_params* p, const void* out, const char* who) {
     if (!m || !p || !offsets || B < 0 || (B > 0 && (!guesses || !out))) return fail(DPG_ERR_ARG, "%s: a NULL argument or B < 0", who);
     if (is_multi(m->ctx)) return fail(DPG_ERR_STATE, "%s runs on a single-device context", who);
     if (dpg_track_params_check(p)) return fail(DPG_ERR_ARG, "%s: a parameter out of range", who);
@@ -137,77 +132,112 @@ extern "C" int dpg_fmap_track(dpg_fmap* m, const float* clouds, const int64_t* o
     const int64_t total = offsets[B] - offsets[0];
     if (total > (int64_t)1 << 26) return fail(DPG_ERR_SIZE, "%s: %lld points in all, at most 2^26", who, (long long)total);
     if (total > 0 && !clouds) return fail(DPG_ERR_ARG, "%s: clouds_xy is NULL", who);
-    if (B == 0) return DPG_OK;
-    const dpg_track_params P = *p;
-    const int64_t A = 2 * (int64_t)P.half_a + 1;
-    // the upload, one block: scans [B] | rot [B][A][2] | the points from offsets[0] on
-    const size_t o_scan = 0, o_rot = align16(o_scan + sizeof(TrackScan) * (size_t)B), o_pts = align16(o_rot + sizeof(float) * 2 * (size_t)(A * B)),
-                 n_in = align16(o_pts + sizeof(float) * 2 * (size_t)total);
+    return DPG_OK;
+}
+
+int track_stage(dpg_fmap* m, const float* clouds, const int64_t* offsets, int64_t B, const float* guesses,
+                const dpg_track_params* p, const char* who, TrackStage& st) {
+    st.P = *p;
+    st.B = B;
+    st.A = 2 * (int64_t)st.P.half_a + 1;
+    st.total = offsets[B] - offsets[0];
+    const int64_t A = st.A;
+    st.o_scan = 0;
+    st.o_rot = align16(st.o_scan + sizeof(TrackScan) * (size_t)B);
+    st.o_pts = align16(st.o_rot + sizeof(float) * 2 * (size_t)(A * B));
+    st.n_in = align16(st.o_pts + sizeof(float) * 2 * (size_t)st.total);
     HIP_TRY(hipSetDevice(m->device));
-    hipStream_t s = m->s;
-    HIP_TRY(hipStreamSynchronize(s));   // the pinned blocks of the previous call are free
-    if (m->h_in.reserve(n_in) || m->h_recs.reserve((size_t)B)) return fail(DPG_ERR_HIP, "%s: out of pinned memory for %lld scans", who, (long long)B);
-    TrackScan* scans = reinterpret_cast<TrackScan*>(m->h_in.p + o_scan);
-    float* rot = reinterpret_cast<float*>(m->h_in.p + o_rot);
+    HIP_TRY(hipStreamSynchronize(m->s));   // the pinned blocks of the previous call are free
+    if (m->h_in.reserve(st.n_in)) return fail(DPG_ERR_HIP, "%s: out of pinned memory for %lld scans", who, (long long)B);
+    st.scans = reinterpret_cast<TrackScan*>(m->h_in.p + st.o_scan);
+    st.rot = reinterpret_cast<float*>(m->h_in.p + st.o_rot);
     dpg_loc_params lp;
     dpg_loc_params_default(&lp);
-    lp.half_a = P.half_a;
-    lp.angle_step = P.angle_step;
+    lp.half_a = st.P.half_a;
+    lp.angle_step = st.P.angle_step;
     for (int64_t b = 0; b < B; ++b) {
         const float* g = guesses + 3 * b;
-        TrackScan& t = scans[b];
+        TrackScan& t = st.scans[b];
         memset(&t, 0, sizeof(t));
         if (!host_key(g[0], m->res, t.cx) || !host_key(g[1], m->res, t.cy) || !std::isfinite(g[2]))
             return fail(DPG_ERR_ARG, "%s: the guess of scan %lld is not finite or its cell key is beyond 2^29", who, (long long)b);
         t.begin = offsets[b] - offsets[0];
         t.end = offsets[b + 1] - offsets[0];
-        dpg_loc_rotations(g[2], &lp, rot + 2 * A * b);
+        dpg_loc_rotations(g[2], &lp, st.rot + 2 * A * b);
     }
-    if (total > 0) memcpy(m->h_in.p + o_pts, clouds + 2 * offsets[0], sizeof(float) * 2 * (size_t)total);
-    const bool empty = m->cells() == 0;
-    if (!empty) {
-        if (m->d_in.reserve(n_in) || m->part.reserve((size_t)(A * B)) || m->at_guess.reserve((size_t)B) || m->recs.reserve((size_t)B))
-            return fail(DPG_ERR_HIP, "%s: out of device memory for %lld scans", who, (long long)B);
-        for (DevEvent& e : m->track_ev)
-            if (e.ensure(hipEventDefault)) return fail(DPG_ERR_HIP, "hipEventCreate failed");
-        HIP_TRY(hipMemcpyAsync(m->d_in.p, m->h_in.p, n_in, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipEventRecord(m->track_ev[0].e, s));
-        TrackDims g;
-        memset(&g, 0, sizeof(g));
-        g.w = m->box[2]; g.h = m->box[3]; g.x0 = m->box[0]; g.y0 = m->box[1];
-        g.hx = P.half_x; g.hy = P.half_y; g.ha = P.half_a;
-        g.A = (int32_t)A; g.wx = 2 * P.half_x + 1; g.n_shifts = g.wx * (2 * P.half_y + 1);
-        g.res = m->res;
-        const TrackScan* d_scans = reinterpret_cast<const TrackScan*>(m->d_in.p + o_scan);
-        track_scan_kernel<<<dim3((unsigned)A, (unsigned)B), kLocT, 0, s>>>(g, d_scans, reinterpret_cast<const float2*>(m->d_in.p + o_pts),
-                                                                         reinterpret_cast<const float*>(m->d_in.p + o_rot), m->field.p,
-                                                                         m->part.p, m->at_guess.p);
-        HIP_TRY(hipGetLastError());
-        track_reduce_kernel<<<(unsigned)B, kLocT, 0, s>>>(g, m->part.p, m->at_guess.p, m->recs.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(m->track_ev[1].e, s));
-        HIP_TRY(hipMemcpyAsync(m->h_recs.p, m->recs.p, sizeof(TrackRec) * (size_t)B, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        (void)hipEventElapsedTime(&m->track_ms, m->track_ev[0].e, m->track_ev[1].e);
-    }
-    for (int64_t b = 0; b < B; ++b) {
+    if (st.total > 0) memcpy(m->h_in.p + st.o_pts, clouds + 2 * offsets[0], sizeof(float) * 2 * (size_t)st.total);
+    return DPG_OK;
+}
+
+int track_launch(dpg_fmap* m, const TrackStage& st, TrackRec* d_recs, const char* who) {
+    const dpg_track_params& P = st.P;
+    const int64_t A = st.A, B = st.B;
+    if (m->part.reserve((size_t)(A * B)) || m->at_guess.reserve((size_t)B))
+        return fail(DPG_ERR_HIP, "%s: out of device memory for %lld scans", who, (long long)B);
+    TrackDims g;
+    memset(&g, 0, sizeof(g));
+    g.w = m->box[2]; g.h = m->box[3]; g.x0 = m->box[0]; g.y0 = m->box[1];
+    g.hx = P.half_x; g.hy = P.half_y; g.ha = P.half_a;
+    g.A = (int32_t)A; g.wx = 2 * P.half_x + 1; g.n_shifts = g.wx * (2 * P.half_y + 1);
+    g.res = m->res;
+    const TrackScan* d_scans = reinterpret_cast<const TrackScan*>(m->d_in.p + st.o_scan);
+    track_scan_kernel<<<dim3((unsigned)A, (unsigned)B), kLocT, 0, m->s>>>(g, d_scans, reinterpret_cast<const float2*>(m->d_in.p + st.o_pts),
+                                                                        reinterpret_cast<const float*>(m->d_in.p + st.o_rot), m->field.p,
+                                                                        m->part.p, m->at_guess.p);
+    HIP_TRY(hipGetLastError());
+    track_reduce_kernel<<<(unsigned)B, kLocT, 0, m->s>>>(g, m->part.p, m->at_guess.p, d_recs);
+    HIP_TRY(hipGetLastError());
+    return DPG_OK;
+}
+
+void track_results(const dpg_fmap* m, const TrackStage& st, const float* guesses, const TrackRec* recs, dpg_track_result* out) {
+    const dpg_track_params& P = st.P;
+    for (int64_t b = 0; b < st.B; ++b) {
         // an empty map: every score is 0, the winner of an all-zero volume
-        const TrackRec rec = empty ? TrackRec{{0, P.half_a, 0, 0}, 0, {0, 0, 0}} : m->h_recs.p[b];
+        const TrackRec rec = recs ? recs[b] : TrackRec{{0, P.half_a, 0, 0}, 0, {0, 0, 0}};
         const float* g = guesses + 3 * b;
-        const float* rt = rot + 2 * A * b;
+        const float* rt = st.rot + 2 * st.A * b;
         dpg_track_result r;
         memset(&r, 0, sizeof(r));
-        r.pose[0] = (float)((double)((int64_t)scans[b].cx + rec.win.dx) * m->res);
-        r.pose[1] = (float)((double)((int64_t)scans[b].cy + rec.win.dy) * m->res);
+        r.pose[0] = (float)((double)((int64_t)st.scans[b].cx + rec.win.dx) * m->res);
+        r.pose[1] = (float)((double)((int64_t)st.scans[b].cy + rec.win.dy) * m->res);
         r.pose[2] = (float)((double)g[2] + (double)(rec.win.a - P.half_a) * (double)P.angle_step);
         r.rot[0] = rt[2 * rec.win.a];
         r.rot[1] = rt[2 * rec.win.a + 1];
         r.score = rec.win.score;
         r.score_at_guess = rec.score_at_guess;
-        r.n_pts = (int32_t)(scans[b].end - scans[b].begin);
+        r.n_pts = (int32_t)(st.scans[b].end - st.scans[b].begin);
         r.best_a = rec.win.a; r.best_dx = rec.win.dx; r.best_dy = rec.win.dy;
         r.status = rec.win.score == 0 ? DPG_LOC_NO_OVERLAP : DPG_LOC_OK;
         out[b] = r;
     }
+}
+
+extern "C" float dpg_fmap_track_kernel_ms(const dpg_fmap* m) { return m ? m->track_ms : 0.f; }
+
+extern "C" int dpg_fmap_track(dpg_fmap* m, const float* clouds, const int64_t* offsets, int64_t B, const float* guesses,
+                              const dpg_track_params* p, dpg_track_result* out) {
+    const char* who = "dpg_fmap_track";
+    if (int rc = track_check(m, clouds, offsets, B, guesses, p, out, who)) return rc;
+    if (B == 0) return DPG_OK;
+    TrackStage st;
+    if (int rc = track_stage(m, clouds, offsets, B, guesses, p, who, st)) return rc;
+    if (m->h_recs.reserve((size_t)B)) return fail(DPG_ERR_HIP, "%s: out of pinned memory for %lld scans", who, (long long)B);
+    const bool empty = m->cells() == 0;
+    if (!empty) {
+        hipStream_t s = m->s;
+        if (m->d_in.reserve(st.n_in) || m->recs.reserve((size_t)B))
+            return fail(DPG_ERR_HIP, "%s: out of device memory for %lld scans", who, (long long)B);
+        for (DevEvent& e : m->track_ev)
+            if (e.ensure(hipEventDefault)) return fail(DPG_ERR_HIP, "hipEventCreate failed");
+        HIP_TRY(hipMemcpyAsync(m->d_in.p, m->h_in.p, st.n_in, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(m->track_ev[0].e, s));
+        if (int rc = track_launch(m, st, m->recs.p, who)) return rc;
+        HIP_TRY(hipEventRecord(m->track_ev[1].e, s));
+        HIP_TRY(hipMemcpyAsync(m->h_recs.p, m->recs.p, sizeof(TrackRec) * (size_t)B, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        (void)hipEventElapsedTime(&m->track_ms, m->track_ev[0].e, m->track_ev[1].e);
+    }
+    track_results(m, st, guesses, empty ? nullptr : m->h_recs.p, out);
     return DPG_OK;
 }

@@ -326,6 +326,36 @@ assert C.sizeof(FmapInfo) == 48
 FMAP_HEADER_SIZE = 64
 
 
+class RefineParams(C.Structure):
+    """dpg_refine_params -- the Gauss-Newton refinement on a frozen map's field (dpg_fmap_refine)."""
+
+    _fields_ = [("max_iters", C.c_int32), ("pad", C.c_int32), ("lambda_", C.c_double), ("max_step_cells", C.c_double),
+                ("max_step_angle", C.c_double), ("tol_cells", C.c_double), ("tol_angle", C.c_double)]
+
+
+class RefineResult(C.Structure):
+    """dpg_refine_result -- the refined pose of one scan with its curvature and covariance."""
+
+    _fields_ = [("pose", C.c_float * 3), ("rot", C.c_float * 2), ("status", C.c_int32), ("n_evals", C.c_int32),
+                ("best_eval", C.c_int32), ("n_used", C.c_int32), ("pad", C.c_int32), ("tu", C.c_double), ("tv", C.c_double),
+                ("c", C.c_double), ("s", C.c_double), ("cost", C.c_double), ("cost_start", C.c_double),
+                ("sum_r", C.c_double), ("hess", C.c_double * 6), ("cov", C.c_double * 6), ("cov_ok", C.c_int32),
+                ("pad2", C.c_int32)]
+
+
+REFINE_RESULT_DTYPE = np.dtype(
+    [("pose", "<f4", (3,)), ("rot", "<f4", (2,)), ("status", "<i4"), ("n_evals", "<i4"), ("best_eval", "<i4"),
+     ("n_used", "<i4"), ("pad", "<i4"), ("tu", "<f8"), ("tv", "<f8"), ("c", "<f8"), ("s", "<f8"), ("cost", "<f8"),
+     ("cost_start", "<f8"), ("sum_r", "<f8"), ("hess", "<f8", (6,)), ("cov", "<f8", (6,)), ("cov_ok", "<i4"),
+     ("pad2", "<i4")], align=True)
+assert REFINE_RESULT_DTYPE.itemsize == C.sizeof(RefineResult) == 200 and C.sizeof(RefineParams) == 48
+REFINE_TRACE_COLS = 16
+DPG_REFINE_CONVERGED = 0
+DPG_REFINE_MAX_ITERS = 1
+DPG_REFINE_DEGENERATE = 2
+DPG_REFINE_NO_POINTS = 3
+
+
 ALLREDUCE_F64 = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int64)
 ALLREDUCE_F32 = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_float), C.c_int64)
 ALLGATHER = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
@@ -474,6 +504,15 @@ SIGNATURES = {
     "dpg_track_params_check": (C.c_int, [C.POINTER(TrackParams)]),
     "dpg_fmap_track": (C.c_int, [P, F32P, I64P, C.c_int64, F32P, C.POINTER(TrackParams), P]),
     "dpg_fmap_track_kernel_ms": (C.c_float, [P]),
+    "dpg_refine_params_default": (None, [C.POINTER(RefineParams)]),
+    "dpg_refine_params_check": (C.c_int, [C.POINTER(RefineParams)]),
+    "dpg_refine_start": (C.c_int, [F32P, F32P]),
+    "dpg_refine_angle": (C.c_float, [C.c_double, C.c_double]),
+    "dpg_fmap_refine": (C.c_int, [P, F32P, I64P, C.c_int64, F32P, C.POINTER(RefineParams), P]),
+    "dpg_fmap_refine_trace": (C.c_int, [P, F32P, I64P, C.c_int64, F32P, C.POINTER(RefineParams), P, F64P, C.c_int64]),
+    "dpg_fmap_track_refine": (C.c_int, [P, F32P, I64P, C.c_int64, F32P, C.POINTER(TrackParams), C.POINTER(RefineParams),
+                                        P, P]),
+    "dpg_fmap_refine_kernel_ms": (C.c_float, [P]),
     "dpg_reoptimize": (C.c_int, [P, C.c_int64, I32P, F32P, F32P, C.POINTER(IcpParams), C.POINTER(GnParams),
                                  C.POINTER(ReoptParams), F64P, C.POINTER(ReoptStats)]),
     "dpg_reoptimize_inc": (C.c_int, [P, C.c_int64, I32P, F32P, F32P, C.POINTER(IcpParams), C.POINTER(ReoptParams),
@@ -603,6 +642,12 @@ def default_loc_params() -> LocParams:
 def default_track_params() -> TrackParams:
     p = TrackParams()
     lib().dpg_track_params_default(C.byref(p))
+    return p
+
+
+def default_refine_params() -> RefineParams:
+    p = RefineParams()
+    lib().dpg_refine_params_default(C.byref(p))
     return p
 
 

@@ -1032,6 +1032,79 @@ class FrozenMap:
                                    _abi.vptr(out)), "dpg_fmap_track")
         return out
 
+    @staticmethod
+    def _batch(clouds, offsets):
+        """(points [N, 2] float32, offsets [B + 1] int64) of a list of clouds or of one array with offsets."""
+        if offsets is None:
+            cl = [_f32(c).reshape(-1, 2) for c in clouds]
+            off = np.zeros(len(cl) + 1, np.int64)
+            off[1:] = np.cumsum([len(c) for c in cl])
+            pts = np.concatenate(cl) if cl else np.zeros((0, 2), np.float32)
+        else:
+            pts = _f32(clouds).reshape(-1, 2)
+            off = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+        return np.ascontiguousarray(pts, np.float32), off
+
+    def refine(self, clouds, starts, params=None, offsets=None, trace=False):
+        """Sub-cell refinement of a batch of scans on the interpolated field (dpg_fmap_refine):
+        REFINE_RESULT_DTYPE records [B].  starts: TRACK_RESULT_DTYPE records (their pose and rot are the
+        start), or [B, 3] poses (x, y, theta) passed through dpg_refine_start, or [B, 5] rows (x, y, theta,
+        c, s).  trace=True returns (records, trace [B, max_iters + 1, 16]) from dpg_fmap_refine_trace."""
+        pts, off = self._batch(clouds, offsets)
+        B = len(off) - 1
+        st = refine_starts(starts)
+        if len(st) != B:
+            raise ValueError(f"refine: {B} scans and {len(st)} starts")
+        p = params or _abi.default_refine_params()
+        out = np.zeros(B, _abi.REFINE_RESULT_DTYPE)
+        if not trace:
+            check(lib().dpg_fmap_refine(self.handle, ptr(pts, C.c_float), ptr(off, C.c_int64), B, ptr(st, C.c_float), C.byref(p),
+                                        _abi.vptr(out)), "dpg_fmap_refine")
+            return out
+        tr = np.zeros((B, int(p.max_iters) + 1, _abi.REFINE_TRACE_COLS), np.float64)
+        check(lib().dpg_fmap_refine_trace(self.handle, ptr(pts, C.c_float), ptr(off, C.c_int64), B, ptr(st, C.c_float), C.byref(p),
+                                          _abi.vptr(out), ptr(tr, C.c_double), tr.size), "dpg_fmap_refine_trace")
+        return out, tr
+
+    def track_refine(self, clouds, guesses, track_params=None, refine_params=None, offsets=None):
+        """track and the refinement of its winners in one enqueue (dpg_fmap_track_refine):
+        (TRACK_RESULT_DTYPE records [B], REFINE_RESULT_DTYPE records [B]), the bytes of track(...) and of
+        refine(clouds, track records)."""
+        pts, off = self._batch(clouds, offsets)
+        B = len(off) - 1
+        g = _f32(guesses).reshape(-1, 3)
+        if len(g) != B:
+            raise ValueError(f"track_refine: {B} scans and {len(g)} guesses")
+        tp = track_params or _abi.default_track_params()
+        rp = refine_params or _abi.default_refine_params()
+        t_out, r_out = np.zeros(B, _abi.TRACK_RESULT_DTYPE), np.zeros(B, _abi.REFINE_RESULT_DTYPE)
+        check(lib().dpg_fmap_track_refine(self.handle, ptr(pts, C.c_float), ptr(off, C.c_int64), B, ptr(g, C.c_float), C.byref(tp),
+                                          C.byref(rp), _abi.vptr(t_out), _abi.vptr(r_out)), "dpg_fmap_track_refine")
+        return t_out, r_out
+
+    def refine_kernel_ms(self) -> float:
+        return float(lib().dpg_fmap_refine_kernel_ms(self.handle))
+
+    def track_kernel_ms(self) -> float:
+        return float(lib().dpg_fmap_track_kernel_ms(self.handle))
+
+
+def refine_starts(starts) -> np.ndarray:
+    """The [B, 5] float32 starts (x, y, theta, c, s) of dpg_fmap_refine from track records (pose, rot),
+    from [B, 3] poses (dpg_refine_start: c and s are the float cosine and sine of theta) or from [B, 5] rows."""
+    a = np.asarray(starts)
+    if a.dtype.names and "pose" in a.dtype.names and "rot" in a.dtype.names:
+        a = np.atleast_1d(a)
+        return np.ascontiguousarray(np.concatenate([a["pose"].reshape(-1, 3), a["rot"].reshape(-1, 2)], 1), np.float32)
+    a = _f32(a)
+    if a.ndim == 2 and a.shape[1] == 5:
+        return np.ascontiguousarray(a)
+    a = np.ascontiguousarray(a.reshape(-1, 3))
+    out = np.zeros((len(a), 5), np.float32)
+    for b in range(len(a)):
+        check(lib().dpg_refine_start(ptr(a[b], C.c_float), ptr(out[b], C.c_float)), "dpg_refine_start")
+    return out
+
 
 class IncGraph:
     """The incremental per-node pose graph (dpg_inc): isam_->update once per new node

@@ -180,6 +180,8 @@ class DpgSLAM:
         self.last_dpg = None                            # dpg_change_stats of the last executeDPG
         self._loc = None                                # localisation-only mode's state (StartLocalization)
         self.last_track = None                          # the record of the last tracked scan
+        self.last_refine = None                         # with field_refine: the refinement's record of that scan
+        self._tracked_cov = None                        # the cov of the last accepted refinement (6 doubles) or None
 
     # ------------------------------------------------------------------ public API
     def ObserveOdometry(self, odom_loc, odom_angle):
@@ -228,7 +230,7 @@ class DpgSLAM:
 
     # ------------------------------------------------------------------ localisation-only mode
     def StartLocalization(self, track_params=None, loc_params=None, fmap=None, pose=None, min_response=0.0,
-                          icp_refine=True):
+                          icp_refine=True, field_refine=None):
         """Localisation-only mode: from here to StopLocalization every ObserveLaser tracks its scan in a
         frozen map (dpg_fmap_track over track_params' window) and creates no node and no factor; the
         store and the graph are not touched.  fmap None: the current active map is frozen
@@ -238,7 +240,12 @@ class DpgSLAM:
         arithmetic); r = fmap.track([cloud], [guess])[0], kept in last_track.  With status DPG_LOC_OK
         and score / (255 n_pts) >= min_response the tracked pose becomes r.pose -- or, with icp_refine,
         the pose of one run_icp of the scan at r.pose against the nearest node that was active at the
-        freeze, when that ICP converges.  Otherwise it is left alone and dead-reckons on."""
+        freeze, when that ICP converges.  Otherwise it is left alone and dead-reckons on.
+        field_refine: a RefineParams (or True for the defaults) replaces the ICP step by the Gauss-Newton
+        refinement on the map's own field: (t, f) = fmap.track_refine([cloud], [guess], track_params,
+        field_refine), kept in last_track and last_refine; when the track is accepted as above and f's
+        status is CONVERGED or MAX_ITERS the tracked pose becomes f.pose, else r.pose.  It needs no node
+        cloud, so it works on a loaded map; GetTrackedPoseCovariance() then returns f's covariance."""
         if pose is None and not len(self.poses):
             raise ValueError("StartLocalization: the graph has no node yet and no pose was given")
         V = len(self.poses)
@@ -254,8 +261,14 @@ class DpgSLAM:
         if getattr(fmap, "track", None) is None:
             raise NotImplementedError(f"StartLocalization needs a `track(clouds, guesses, params)` method on the map; "
                                       f"{type(fmap).__name__} has none")
+        refine = None
+        if field_refine is not None and field_refine is not False:
+            if getattr(fmap, "track_refine", None) is None:
+                raise NotImplementedError(f"StartLocalization(field_refine=...) needs a `track_refine(clouds, guesses, track_params, "
+                                          f"refine_params)` method on the map; {type(fmap).__name__} has none")
+            refine = _abi.default_refine_params() if field_refine is True else field_refine
         icp = None
-        if icp_refine:
+        if icp_refine and refine is None:
             icp = getattr(getattr(self.be, "ctx", None), "run_icp", None)
             if icp is None:
                 raise NotImplementedError(f"StartLocalization(icp_refine=True) needs a `ctx.run_icp` on the backend; "
@@ -268,7 +281,9 @@ class DpgSLAM:
             loc, ang = self.GetPose()
             pose = (loc[0], loc[1], ang)
         self.last_track = None
-        self._loc = dict(fmap=fmap, own=own, params=track_params, min_response=float(min_response), icp=icp,
+        self.last_refine = None
+        self._tracked_cov = None
+        self._loc = dict(fmap=fmap, own=own, params=track_params, min_response=float(min_response), icp=icp, refine=refine,
                          nodes=nodes, node_poses=self.poses[nodes].copy(), pose=np.asarray(pose, f32).reshape(3).copy(),
                          odom_ref=self.prev_odom.copy() if self.odom_initialized else None)
 
@@ -278,6 +293,7 @@ class DpgSLAM:
         if self._loc is not None and self._loc["own"]:
             self._loc["fmap"].close()
         self._loc = None
+        self._tracked_cov = None
 
     def _tracked_pose(self):
         """The tracked pose plus the odometry since it was set."""
@@ -293,13 +309,25 @@ class DpgSLAM:
         cloud = api.scan_to_cloud(ranges, angle_min, angle_max, range_max, self.laser)
         loc, ang = self._tracked_pose()
         guess = np.array([loc[0], loc[1], ang], f32)
-        r = m["fmap"].track([cloud], [guess], m["params"])[0]
+        f = None
+        if m["refine"] is not None:
+            t, fr = m["fmap"].track_refine([cloud], [guess], m["params"], m["refine"])
+            r, f = t[0], fr[0]
+            self.last_refine = f
+        else:
+            r = m["fmap"].track([cloud], [guess], m["params"])[0]
         self.last_track = r
         response = float(r["score"]) / (255.0 * max(int(r["n_pts"]), 1))
         if int(r["status"]) != _abi.DPG_LOC_OK or response < m["min_response"]:
             return                                  # the tracked pose dead-reckons on
         pose = np.array(r["pose"], f32)
-        if m["icp"] is not None and len(m["nodes"]):
+        if f is not None:
+            self._tracked_cov = None
+            if int(f["status"]) in (_abi.DPG_REFINE_CONVERGED, _abi.DPG_REFINE_MAX_ITERS):
+                pose = np.array(f["pose"], f32)
+                if int(f["cov_ok"]):
+                    self._tracked_cov = np.array(f["cov"], np.float64)
+        elif m["icp"] is not None and len(m["nodes"]):
             d = m["node_poses"][:, :2].astype(np.float64) - pose[:2].astype(np.float64)
             k = int(np.argmin(d[:, 0] ** 2 + d[:, 1] ** 2))
             t = int(m["nodes"][k])
@@ -308,6 +336,17 @@ class DpgSLAM:
                 pose = api.transform_point(np.array([z[0][0], z[0][1], z[1]], f32), m["node_poses"][k])
         m["pose"] = pose
         m["odom_ref"] = self.prev_odom.copy() if self.odom_initialized else None
+
+    def GetTrackedPoseCovariance(self):
+        """The 3x3 covariance (x, y, theta; metres and radians, the map's frame) of the last accepted
+        field refinement of localisation-only mode (dpg_refine_result.cov), or None when there is none --
+        no field_refine, no accepted refinement yet, the last accepted track fell back to the track's
+        pose, or cov_ok is 0.  It is the least-squares curvature estimate in the field's own residual
+        units, not a calibrated sensor model."""
+        c = self._tracked_cov
+        if c is None:
+            return None
+        return np.array([[c[0], c[1], c[2]], [c[1], c[3], c[4]], [c[2], c[4], c[5]]], np.float64)
 
     def GetPoseCovariance(self, node=None):
         """The 3x3 marginal covariance of a node's pose (default: the latest node), in the pose's own

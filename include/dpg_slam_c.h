@@ -1141,6 +1141,142 @@ int dpg_fmap_track(dpg_fmap* m, const float* clouds_xy, const int64_t* offsets, 
 /* ms of the two launches of the last dpg_fmap_track that launched anything (HIP events) */
 float dpg_fmap_track_kernel_ms(const dpg_fmap* m);
 
+/* dpg_fmap_refine: sub-cell pose refinement of a batch of scans on the map's interpolated field -- a
+ * few damped Gauss-Newton steps per scan from a start such as a tracked pose, on the device for the
+ * whole batch, with the curvature matrix of the answer.  It reads only F, the box and res, so it
+ * works on a loaded map.  The reference has no such stage.  This comment is the contract: the kernel
+ * (csrc/dpg_refine.hip) and the numpy restatement (tests/refine_ref.py) are written from it and share
+ * no code.  Every fp64 expression below is one rounding per operation (no contraction, no fast-math);
+ * the device uses no transcendental and no square root.  Parentheses fix the order.
+ *
+ * Map.  F uint8 [h][w], box (x0, y0, w, h) and res are the handle's.  Outside the box F reads 0.  An
+ *   empty map is not special: every sample reads 0.
+ * Start of scan b.  starts[b][5] floats (x, y, theta, c, s): the first five floats of a
+ *   dpg_track_result (pose, rot); theta is not read.
+ *     ires = 1.0 / res
+ *     tu = ((double)x ires) - (double)x0        tv = ((double)y ires) - (double)y0
+ *     c = (double)starts[3]   s = (double)starts[4]          (not normalised)
+ *   DPG_ERR_ARG when x, y, c or s is not finite, when |(double)x ires| >= 2^29 (or y), or when
+ *   (c c) + (s s) is outside [0.5, 2].
+ *   dpg_refine_start (host): out = (x, y, theta, (float)cos((double)theta), (float)sin((double)theta)),
+ *   dpg_loc_rotations' rule.
+ * Evaluation at state (tu, tv, c, s).  Point i is float (x, y); it is used iff both coordinates are
+ *   finite and |u|, |v| < 2^29; an unused point adds nothing.
+ *     px = (double)x ires            py = (double)y ires
+ *     rx = (c px) - (s py)           ry = (s px) + (c py)
+ *     u = rx + tu                    v = ry + tv
+ *     iu = floor(u), fu = u - iu     iv = floor(v), fv = v - iv     au = 1 - fu, av = 1 - fv
+ *     F00 = F[iv][iu]  F10 = F[iv][iu+1]  F01 = F[iv+1][iu]  F11 = F[iv+1][iu+1]      (as doubles)
+ *     M  = (av ((au F00) + (fu F10))) + (fv ((au F01) + (fu F11)))
+ *     gu = (av (F10 - F00)) + (fv (F11 - F01))
+ *     gv = (au (F01 - F00)) + (fu (F11 - F10))
+ *     r  = 255 - M                   jt = (gv rx) - (gu ry)
+ *   Eleven sums S: gu gu, gu gv, gu jt, gv gv, gv jt, jt jt (H00 H01 H02 H11 H12 H22: the upper
+ *   triangle, in cells and radians), gu r, gv r, jt r (b0 b1 b2), r r (cost), r.  n_used is an integer
+ *   count beside them.
+ * Summation order, 256 lanes.  Lane t adds its points i = t, t + 256, ... in ascending order, each sum
+ *   from +0.0.  Within each group of 64 lanes, for stride 32, 16, 8, 4, 2, 1: p[l] += p[l + stride]
+ *   for l < stride.  The total is (W0 + W1) + (W2 + W3) over the four groups' lane-0 values.
+ * Step from S, with params' lambda, max_step_cells, max_step_angle, tol_cells, tol_angle and
+ *   eps = 1e-12:
+ *     D1 = H11 + (lambda H11)          D2 = H22 + (lambda H22)
+ *     d0 = H00 + (lambda H00)                                   pivot: d0 > 0
+ *     l10 = H01/d0    l20 = H02/d0
+ *     d1 = D1 - (l10 H01)                                       pivot: d1 > eps D1
+ *     e12 = H12 - (l20 H01)            l21 = e12/d1
+ *     d2 = (D2 - (l20 H02)) - (l21 e12)                         pivot: d2 > eps D2
+ *     y0 = b0    y1 = b1 - (l10 y0)    y2 = (b2 - (l20 y0)) - (l21 y1)
+ *     z2 = y2/d2    z1 = (y1/d1) - (l21 z2)    z0 = ((y0/d0) - (l10 z1)) - (l20 z2)
+ *   A failed pivot or a non-finite z: DEGENERATE.  du, dv = z0, z1 clamped to +-max_step_cells,
+ *   dt = z2 clamped to +-max_step_angle.  Converged when |du| < tol_cells and |dv| < tol_cells and
+ *   |dt| < tol_angle; the step is then not applied.  Apply: tu += du; tv += dv; a = dt 0.5; q = a a;
+ *   den = 1 + q; cd = (1 - q)/den; sd = (a + a)/den; (c, s) <- ((c cd) - (s sd), (s cd) + (c sd)) -- the
+ *   Cayley form, an exact rotation without trigonometry.
+ * Loop, for k = 0 .. max_iters: 1. evaluate at iterate k; 2. if k == 0 or cost_k < best.cost (strict:
+ *   the earlier iterate wins a tie), best = (k, state, S, n_used); 3. n_used == 0 at k = 0 stops with
+ *   NO_POINTS; 4. k == max_iters stops with MAX_ITERS; 5. otherwise the step, which may stop with
+ *   DEGENERATE or CONVERGED.  The answer is `best`: a refinement never returns a worse cost than its
+ *   start.  n_evals is the number of evaluations made.
+ * Record (host, plain C): pose x = (float)((tu + (double)x0) res), y alike; theta =
+ *   dpg_refine_angle(c, s) = (float)atan2(s, c); rot = ((float)c, (float)s); cost = S[9], sum_r = S[10]
+ *   and hess = S[0..5] of the best iterate, undamped; cost_start = the cost of evaluation 0.
+ *   cov = s2 H^-1 in metres and radians: s2 = cost / (double)max(n_used - 3, 1); column j of H^-1 is
+ *   the z of the step's expressions at lambda = 0 for b = the unit vector e_j, and entry (i, j), i <= j,
+ *   is taken from column j; cov = ((s2 h00) (res res), (s2 h01) (res res), (s2 h02) res,
+ *   (s2 h11) (res res), (s2 h12) res, s2 h22).  A failed pivot or a non-finite entry: cov_ok = 0 and
+ *   zeros.  cov is the least-squares curvature estimate in the field's own residual units (bytes of
+ *   F), not a calibrated sensor model: it ranks directions and scans, it is not a metric variance.
+ * Calls.  Single-device contexts only (DPG_ERR_STATE).  Every error is raised before anything is
+ *   launched or written.  B = 0 launches nothing.  One upload, one copy back and one synchronisation
+ *   per call, whatever B is.  Limits as dpg_fmap_track: B <= 65535, a scan <= 2^23 points, <= 2^26
+ *   points in all (DPG_ERR_SIZE); DPG_ERR_ARG for NULL arguments, B < 0, bad offsets, parameters out
+ *   of range, or a start as above.  Two calls give the same bytes. */
+typedef struct dpg_refine_params {
+    int32_t max_iters;          /* steps at most, default 20; 0 .. 64 */
+    int32_t pad;
+    double lambda;              /* Levenberg damping of the diagonal, default 1e-3; finite, >= 0 */
+    double max_step_cells;      /* default 1.0; > 0 */
+    double max_step_angle;      /* radians, default 0.02; > 0 */
+    double tol_cells;           /* default 1e-3; >= 0 */
+    double tol_angle;           /* default 1e-5; >= 0 */
+} dpg_refine_params;
+#define DPG_REFINE_CONVERGED 0
+#define DPG_REFINE_MAX_ITERS 1
+#define DPG_REFINE_DEGENERATE 2
+#define DPG_REFINE_NO_POINTS 3
+typedef struct dpg_refine_result {
+    float pose[3];              /* x, y, theta of the best iterate, in the map's frame */
+    float rot[2];               /* ((float)c, (float)s) */
+    int32_t status;             /* DPG_REFINE_* */
+    int32_t n_evals;            /* evaluations made, 1 .. max_iters + 1 */
+    int32_t best_eval;          /* the evaluation the answer is from */
+    int32_t n_used;             /* points used by that evaluation */
+    int32_t pad;
+    double tu, tv, c, s;        /* the best iterate's state, in cells */
+    double cost, cost_start;    /* sum of r r at the best iterate and at evaluation 0 */
+    double sum_r;
+    double hess[6];             /* H00 H01 H02 H11 H12 H22, cells and radians, undamped */
+    double cov[6];              /* xx xy xt yy yt tt, metres and radians (see above) */
+    int32_t cov_ok;
+    int32_t pad2;
+} dpg_refine_result;
+#define DPG_REFINE_PARAMS_SIZE 48
+#define DPG_REFINE_RESULT_SIZE 200
+#define DPG_REFINE_TRACE_COLS 16
+#ifdef __cplusplus
+ static_assert(sizeof(dpg_refine_params) == DPG_REFINE_PARAMS_SIZE && sizeof(dpg_refine_result) == DPG_REFINE_RESULT_SIZE,
+               "refine ABI structs");
+#else
+ _Static_assert(sizeof(dpg_refine_params) == DPG_REFINE_PARAMS_SIZE && sizeof(dpg_refine_result) == DPG_REFINE_RESULT_SIZE,
+                "refine ABI structs");
+#endif
+void dpg_refine_params_default(dpg_refine_params* p);
+/* Host.  DPG_OK or DPG_ERR_ARG: every field against the ranges above (NaN and inf are out of range). */
+int dpg_refine_params_check(const dpg_refine_params* p);
+/* Host.  The start of a pose: out = (x, y, theta, (float)cos((double)theta), (float)sin((double)theta)). */
+int dpg_refine_start(const float pose[3], float out[5]);
+/* Host.  (float)atan2(s, c): the record's theta. */
+float dpg_refine_angle(double c, double s);
+int dpg_fmap_refine(dpg_fmap* m, const float* clouds_xy, const int64_t* offsets, int64_t B, const float* starts,
+                    const dpg_refine_params* params, dpg_refine_result* out);
+/* dpg_fmap_refine with a diagnostic output: trace[B][max_iters + 1][16] doubles, per evaluation
+ * tu, tv, c, s, the eleven sums and n_used as a double; rows past n_evals are zero.  cap in doubles:
+ * DPG_ERR_SIZE with nothing written when it is below B (max_iters + 1) 16. */
+int dpg_fmap_refine_trace(dpg_fmap* m, const float* clouds_xy, const int64_t* offsets, int64_t B, const float* starts,
+                          const dpg_refine_params* params, dpg_refine_result* out, double* trace, int64_t cap);
+/* dpg_fmap_track and the refinement of its winners, enqueued back to back with no host
+ * synchronisation in between: the start of scan b is derived on the device from its track record by
+ * the expressions above (x = (float)((double)(cx + best_dx) res), y alike, (c, s) = the winner's rot).
+ * track_out is byte for byte dpg_fmap_track's, refine_out byte for byte dpg_fmap_refine's of
+ * track_out.  A scan whose track status is DPG_LOC_NO_OVERLAP is refined all the same: the caller
+ * decides what to do with it.  Errors as the two calls; a guess so far out that some shift of its
+ * window would make a start beyond 2^29 cells is DPG_ERR_ARG. */
+int dpg_fmap_track_refine(dpg_fmap* m, const float* clouds_xy, const int64_t* offsets, int64_t B, const float* guesses,
+                          const dpg_track_params* track_params, const dpg_refine_params* refine_params,
+                          dpg_track_result* track_out, dpg_refine_result* refine_out);
+/* ms of the refinement launch of the last call that launched one (HIP events) */
+float dpg_fmap_refine_kernel_ms(const dpg_fmap* m);
+
 #ifdef __cplusplus
 }
 #endif
