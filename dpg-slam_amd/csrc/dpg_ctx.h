@@ -243,6 +243,13 @@ struct dpg_ctx {
     DevBuf<int32_t> csm_diag;
     DevEvent csm_ev[2];
     bool csm_timed = false;
+    // loop-closure verification (dpg_verify.hip): pair records, the counts [pair][direction][4], the
+    // diagnostic table bytes; the events around its kernel
+    DevBuf<dpg_verify_pair> ver_pairs;
+    DevBuf<int32_t> ver_counts;
+    DevBuf<uint8_t> ver_diag;
+    DevEvent ver_ev[2];
+    bool ver_timed = false;
 };
 
 // The rank form over the caller's collectives (kCollHost) in the pipelined Gauss-Newton loop: the

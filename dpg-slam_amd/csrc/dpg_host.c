@@ -14,6 +14,7 @@
  */
 #include <math.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "../../include/dpg_slam_c.h"
@@ -213,6 +214,45 @@ int dpg_csm_rotations(const float guess[6], const dpg_csm_params* p, float* rot_
         rot_out[2 * a + 1] = (float)sin(ang);
     }
     return DPG_OK;
+}
+
+/* ---- loop-closure verification: parameters, sensor key, LDS bytes (the contract is in
+ * include/dpg_slam_c.h) ---- */
+void dpg_verify_params_default(dpg_verify_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->resolution = 0.1f;
+    p->half_cells = 160;
+    p->occ_radius = 2;
+    p->sensor[0] = 0.2f;
+    p->sensor[1] = 0.0f;
+}
+
+int dpg_verify_sensor_key(const dpg_verify_params* p, int32_t key[2]) {
+    if (!p || !key || !(p->resolution > 0.0f) || !isfinite(p->resolution)) return DPG_ERR_ARG;
+    for (int k = 0; k < 2; ++k) {
+        const double q = (double)p->sensor[k] / (double)p->resolution;
+        if (!(fabs(q) < 536870912.0)) return DPG_ERR_ARG;   /* non-finite too */
+        key[k] = (int32_t)round(q);
+    }
+    return DPG_OK;
+}
+
+int dpg_verify_params_check(const dpg_verify_params* p) {
+    int32_t a[2];
+    if (dpg_verify_sensor_key(p, a)) return DPG_ERR_ARG;
+    if (p->half_cells < 0 || p->occ_radius < 0 || p->occ_radius > 7) return DPG_ERR_ARG;
+    if (abs(a[0]) > p->half_cells || abs(a[1]) > p->half_cells) return DPG_ERR_ARG;
+    return DPG_OK;
+}
+
+int64_t dpg_verify_lds_bytes(const dpg_verify_params* p) {
+    if (dpg_verify_params_check(p)) return DPG_ERR_ARG;
+    if (p->half_cells > DPG_VERIFY_LDS_BUDGET) return DPG_ERR_ARG;   /* the product below stays in int64 */
+    const int64_t w = 2 * (int64_t)p->half_cells + 1;
+    const int64_t plane = ((w * w + 31) / 32 * 4 + 15) / 16 * 16;
+    const int64_t bytes = 2 * plane + DPG_VERIFY_LDS_FIXED;
+    return bytes <= DPG_VERIFY_LDS_BUDGET ? bytes : DPG_ERR_ARG;
 }
 
 /* ---- localisation in the active map: parameters and rotations (the contract is in

@@ -115,6 +115,15 @@ typedef struct dpg_csm_pair {
     int32_t pad[2];
 } dpg_csm_pair;
 
+/* One pair of the loop-closure verification as its kernel sees it (dpg_verify.hip; 48 B).  Offsets and
+   counts are in points of the downsampled store. */
+typedef struct dpg_verify_pair {
+    int64_t tgt_off, src_off;
+    int32_t n_tgt, n_src;
+    float c, s, tx, ty;              /* T[0], T[3], T[2], T[5] of the alignment under test */
+    int32_t pad[2];
+} dpg_verify_pair;
+
 /* Pose-graph system on device as the kernels and launchers of dpg_gn.hip see it: a view, raw
    pointers into buffers that the batch graph (GnGraph, dpg_ctx.h) or the incremental graph
    (dpg_inc.hip) owns. */

@@ -265,6 +265,28 @@ DPG_CSM_OK = 0
 DPG_CSM_NO_OVERLAP = 1
 
 
+class VerifyParams(C.Structure):
+    """dpg_verify_params -- raster, occupied radius and sensor position of the loop-closure verification."""
+
+    _fields_ = [("resolution", C.c_float), ("half_cells", C.c_int32), ("occ_radius", C.c_int32),
+                ("sensor", C.c_float * 2), ("pad", C.c_int32 * 3)]
+
+
+class VerifyResult(C.Structure):
+    """dpg_verify_result -- per direction the moving cloud's points, those on the table, on occupied and on free cells."""
+
+    _fields_ = [("n_pts", C.c_int32 * 2), ("n_in", C.c_int32 * 2), ("n_support", C.c_int32 * 2),
+                ("n_free", C.c_int32 * 2), ("status", C.c_int32), ("pad", C.c_int32 * 7)]
+
+
+VERIFY_RESULT_DTYPE = np.dtype(
+    [("n_pts", "<i4", (2,)), ("n_in", "<i4", (2,)), ("n_support", "<i4", (2,)), ("n_free", "<i4", (2,)),
+     ("status", "<i4"), ("pad", "<i4", (7,))], align=True)
+assert VERIFY_RESULT_DTYPE.itemsize == C.sizeof(VerifyResult) == 64 and C.sizeof(VerifyParams) == 32
+DPG_VERIFY_OK = 0
+DPG_VERIFY_NO_OVERLAP = 1
+
+
 class LocParams(C.Structure):
     """dpg_loc_params -- field, window and pruning of the localisation in the active map."""
 
@@ -481,6 +503,13 @@ SIGNATURES = {
     "dpg_csm_scores": (C.c_int, [P, C.c_int32, C.c_int32, F32P, C.POINTER(CsmParams), I32P, C.c_int64]),
     "dpg_csm_kernel_ms": (C.c_float, [P]),
     "dpg_icp_batch_prepare_guess": (C.c_int, [P, I32P, C.c_int64, F32P, C.POINTER(IcpParams)]),
+    "dpg_verify_params_default": (None, [C.POINTER(VerifyParams)]),
+    "dpg_verify_params_check": (C.c_int, [C.POINTER(VerifyParams)]),
+    "dpg_verify_lds_bytes": (C.c_int64, [C.POINTER(VerifyParams)]),
+    "dpg_verify_sensor_key": (C.c_int, [C.POINTER(VerifyParams), I32P]),
+    "dpg_verify_batch": (C.c_int, [P, I32P, C.c_int64, F32P, C.POINTER(VerifyParams), P, C.c_int64]),
+    "dpg_verify_table": (C.c_int, [P, C.c_int32, C.POINTER(VerifyParams), U8P, C.c_int64]),
+    "dpg_verify_kernel_ms": (C.c_float, [P]),
     "dpg_loc_params_default": (None, [C.POINTER(LocParams)]),
     "dpg_loc_params_check": (C.c_int, [C.POINTER(LocParams)]),
     "dpg_loc_rotations": (C.c_int, [C.c_float, C.POINTER(LocParams), F32P]),
@@ -630,6 +659,12 @@ def default_grid_params() -> GridParams:
 def default_csm_params() -> CsmParams:
     p = CsmParams()
     lib().dpg_csm_params_default(C.byref(p))
+    return p
+
+
+def default_verify_params() -> VerifyParams:
+    p = VerifyParams()
+    lib().dpg_verify_params_default(C.byref(p))
     return p
 
 

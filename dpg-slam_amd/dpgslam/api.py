@@ -161,6 +161,39 @@ def csm_lds_bytes(params=None) -> int:
     return n
 
 
+def verify_params_valid(params) -> bool:
+    """dpg_verify_params_check (host): every field inside its range and the sensor's cell inside the table."""
+    return lib().dpg_verify_params_check(C.byref(params)) == _abi.DPG_OK
+
+
+def verify_sensor_key(params=None) -> tuple:
+    """dpg_verify_sensor_key (host): the cell key (ax, ay) of the params' sensor position."""
+    p = params or _abi.default_verify_params()
+    k = np.zeros(2, np.int32)
+    check(lib().dpg_verify_sensor_key(C.byref(p), ptr(k, C.c_int32)), "dpg_verify_sensor_key")
+    return int(k[0]), int(k[1])
+
+
+def verify_lds_bytes(params=None) -> int:
+    """dpg_verify_lds_bytes (host): the verification kernel's LDS working set; raises for invalid
+    params or a table above the budget."""
+    p = params or _abi.default_verify_params()
+    n = int(lib().dpg_verify_lds_bytes(C.byref(p)))
+    if n < 0:
+        raise _abi.DpgError(f"dpg_verify_lds_bytes failed ({n}): invalid parameters or above the LDS budget")
+    return n
+
+
+def verify_accept(records, max_free_fraction=0.15, min_support_fraction=0.25) -> np.ndarray:
+    """Which verification records (VERIFY_RESULT_DTYPE, any shape) pass: status DPG_VERIFY_OK and, in
+    both directions, n_free / n_in <= max_free_fraction and n_support / n_in >= min_support_fraction.
+    Bool array of the records' shape."""
+    r = np.asarray(records)
+    den = np.maximum(r["n_in"], 1).astype(np.float64)   # n_in = 0 comes with status NO_OVERLAP
+    free, sup = r["n_free"] / den, r["n_support"] / den
+    return (r["status"] == _abi.DPG_VERIFY_OK) & (free <= float(max_free_fraction)).all(-1) & (sup >= float(min_support_fraction)).all(-1)
+
+
 def odometry_factor(odom_prev, odom_cur, i_prev, i_cur, motion=(0.4, 0.4, 0.4, 0.4)):
     a, b = _f32(odom_prev), _f32(odom_cur)
     f = _abi.Factor()
@@ -497,6 +530,34 @@ class Context:
 
     def csm_kernel_ms(self) -> float:
         return float(lib().dpg_csm_kernel_ms(self.handle))
+
+    # ---- loop-closure verification (is an alignment consistent with what both scans saw through?) ----
+    def verify_batch(self, edges, transforms, params=None) -> np.ndarray:
+        """dpg_verify_batch over the uploaded scans: per edge (target, source) and its alignment
+        transforms[e] ([E, 6], rows as an ICP result's T) the free-space consistency counts of both
+        directions.  Returns a structured array (_abi.VERIFY_RESULT_DTYPE): n_pts, n_in, n_support,
+        n_free (each [2]: source into the target's table, target into the source's) and status."""
+        p = params or _abi.default_verify_params()
+        e = np.ascontiguousarray(edges, np.int32).reshape(-1, 2)
+        T = _f32(transforms).reshape(-1, 6)
+        if len(T) != len(e):
+            raise ValueError(f"verify_batch: {len(e)} edges but {len(T)} transforms")
+        out = np.zeros(len(e), _abi.VERIFY_RESULT_DTYPE)
+        check(lib().dpg_verify_batch(self.handle, ptr(e, C.c_int32), len(e), ptr(T, C.c_float), C.byref(p), vptr(out),
+                                     len(out)), "dpg_verify_batch")
+        return out
+
+    def verify_table(self, node: int, params=None) -> np.ndarray:
+        """Diagnostic: the state of every cell of one node's table as the kernel built it (0 unknown,
+        1 free, 2 occupied), uint8 [2 half_cells + 1, 2 half_cells + 1], row v, column u."""
+        p = params or _abi.default_verify_params()
+        w = 2 * max(int(p.half_cells), 0) + 1
+        out = np.zeros((w, w), np.uint8)
+        check(lib().dpg_verify_table(self.handle, int(node), C.byref(p), ptr(out, C.c_uint8), out.size), "dpg_verify_table")
+        return out
+
+    def verify_kernel_ms(self) -> float:
+        return float(lib().dpg_verify_kernel_ms(self.handle))
 
     def icp_kernel_ms(self) -> float:
         return float(lib().dpg_icp_batch_kernel_ms(self.handle))

@@ -919,6 +919,92 @@ float dpg_csm_kernel_ms(dpg_ctx* ctx);
 int dpg_icp_batch_prepare_guess(dpg_ctx* ctx, const int32_t* edges, int64_t n_edges, const float* guesses,
                                 const dpg_icp_params* params);
 
+/* ---- loop-closure verification: is an alignment consistent with what both scans saw through? ----
+ * ICP reports `converged` for an alignment that slid into a wrong local minimum too, and every
+ * converged loop closure becomes a factor.  dpg_verify_batch checks an alignment T of a pair (target t,
+ * source s) by free-space consistency (Olson's and Cartographer's visibility test): where t's scan
+ * looked through a cell to something behind it, s's scan placed by T must have no return, and the
+ * reverse.  It needs nothing but the two clouds of the scan store and T.  The reference has no such
+ * stage.  After one float transform per point all work is integer, so every output is exact and
+ * independent of point order.
+ *
+ *   key of a coordinate v (float): round((double)v / res), C round, res widened from float -- the scan
+ *     matcher's rule.  A point with a non-finite coordinate or |(double)v / res| >= 2^29 contributes
+ *     nothing, as model and as moving point.
+ *   Sensor key a = (ax, ay): the key of `sensor`, the lidar's position in the cloud's own frame;
+ *     |ax|, |ay| <= half_cells (H).
+ *   Table of a model cloud, cell keys in [-H, H]^2 in the cloud's own frame, from two sets of cells:
+ *     OCC: every table cell at squared cell distance <= occ_radius^2 (R) from the key of a valid model
+ *       point.  A point whose own key lies outside the table still spreads into it.
+ *     FREE: for every valid model point with key b, d = b - a and n = max(|dx|, |dy|): the cells
+ *       a + (off(dx, n, i), off(dy, n, i)), i = 0 .. n - 1, that lie in the table, where
+ *       off(d, n, i) = sign(d) floor((2 i |d| + n) / (2 n)) in 64-bit integers (i d / n rounded half
+ *       up in magnitude).  The end cell i = n is not marked; n = 0 marks nothing.  Along the longer
+ *       axis off = i, and |ax|, |ay| <= H, so every cell with i > 2H lies outside the table: the loop
+ *       may stop at min(n, 2H + 1) with the same result, and does.
+ *     State of a cell: 2 if in OCC, else 1 if in FREE, else 0.  Occupied wins.
+ *   Moving points under T (rows as dpg_icp_result.T / dpg_icp_guess write them): c = T[0], s = T[3],
+ *     tx = T[2], ty = T[5], as they stand (not normalised), in float, one rounding per operation.
+ *     Direction 0, a source point (x, y) into the target's frame against the target's table:
+ *       qx = ((c x) - (s y)) + tx, qy = ((s x) + (c y)) + ty.
+ *     Direction 1, a target point into the source's frame against the source's table:
+ *       dx = x - tx, dy = y - ty, qx = (c dx) + (s dy), qy = (c dy) - (s dx).
+ *   Counts per direction d: n_pts[d] the points of the moving cloud; n_in[d] its valid points whose
+ *     key lies in the table; n_support[d] those of n_in[d] on state 2; n_free[d] those on state 1;
+ *     the rest of n_in[d] is unknown.
+ * One workgroup per (pair, direction) with the model's table in LDS as two bit planes (OCC, FREE):
+ *   dpg_verify_lds_bytes = 2 round_up_16(4 ceil((2 half_cells + 1)^2 / 32)) + DPG_VERIFY_LDS_FIXED
+ *                          <= DPG_VERIFY_LDS_BUDGET
+ * (the fixed part: one chunk of model keys, the counters). */
+typedef struct dpg_verify_params {
+    float resolution;       /* m per cell, default 0.1; finite, > 0 */
+    int32_t half_cells;     /* H, default 160; the table covers keys [-H, H]^2; >= 0 */
+    int32_t occ_radius;     /* R, cells, default 2; 0 .. 7 */
+    float sensor[2];        /* the lidar in the cloud's frame, default (0.2, 0): dpg_store_params.laser; finite, key within the table */
+    int32_t pad[3];
+} dpg_verify_params;
+
+#define DPG_VERIFY_OK 0
+#define DPG_VERIFY_NO_OVERLAP 1   /* n_in[0] == 0 || n_in[1] == 0: a direction has no point on the other's table */
+typedef struct dpg_verify_result {
+    int32_t n_pts[2], n_in[2], n_support[2], n_free[2];   /* [direction] */
+    int32_t status;         /* DPG_VERIFY_* */
+    int32_t pad[7];
+} dpg_verify_result;
+
+#define DPG_VERIFY_PARAMS_SIZE 32
+#define DPG_VERIFY_RESULT_SIZE 64
+#define DPG_VERIFY_LDS_FIXED 4160
+#define DPG_VERIFY_LDS_BUDGET 163840
+#ifdef __cplusplus
+ static_assert(sizeof(dpg_verify_params) == DPG_VERIFY_PARAMS_SIZE && sizeof(dpg_verify_result) == DPG_VERIFY_RESULT_SIZE, "verify ABI structs");
+#else
+ _Static_assert(sizeof(dpg_verify_params) == DPG_VERIFY_PARAMS_SIZE && sizeof(dpg_verify_result) == DPG_VERIFY_RESULT_SIZE, "verify ABI structs");
+#endif
+
+void dpg_verify_params_default(dpg_verify_params* p);
+/* Host.  DPG_OK, or DPG_ERR_ARG for a field outside its range, a non-finite sensor or a sensor key
+ * outside the table. */
+int dpg_verify_params_check(const dpg_verify_params* p);
+/* Host.  The kernel's LDS bytes by the formula above; DPG_ERR_ARG for params that fail the check or a
+ * working set above DPG_VERIFY_LDS_BUDGET (every dpg_verify_* call checks its params through this). */
+int64_t dpg_verify_lds_bytes(const dpg_verify_params* p);
+/* Host.  key[2] = the sensor key (ax, ay). */
+int dpg_verify_sensor_key(const dpg_verify_params* p, int32_t key[2]);
+/* The check of n_edges alignments, edges[e] = {target, source} over the uploaded scan store with
+ * transforms[e][6] (typically dpg_icp_result.T of that pair), on the context stream: one upload, one
+ * launch (both directions of every pair), one copy back; blocks until results_out[n_edges] is
+ * written.  n_edges = 0 launches nothing.  Errors, each raised before anything is launched or
+ * written: DPG_ERR_ARG -- params, an edge naming a missing node; DPG_ERR_STATE -- no scans uploaded,
+ * or a multi-device, virtual or rank context; DPG_ERR_SIZE -- cap < n_edges. */
+int dpg_verify_batch(dpg_ctx* ctx, const int32_t* edges, int64_t n_edges, const float* transforms,
+                     const dpg_verify_params* params, dpg_verify_result* results_out, int64_t cap);
+/* Diagnostic: the state bytes (0 / 1 / 2) of one node's table as the kernel built it,
+ * (2 half_cells + 1)^2 bytes, row-major with v outer; cap in bytes, DPG_ERR_SIZE when smaller. */
+int dpg_verify_table(dpg_ctx* ctx, int32_t node, const dpg_verify_params* params, uint8_t* out, int64_t cap);
+/* Device time of the last dpg_verify_batch / _table kernel (ms, HIP events); < 0 before one. */
+float dpg_verify_kernel_ms(dpg_ctx* ctx);
+
 /* ---- localisation of one scan in the active map: where a pass starts ----
  * The first node of every pass is created at (0, 0, 0) (createNewPassFirstNode), so a pass has to
  * begin where pass 0 began.  dpg_map_localize matches ONE scan against the whole active map -- the
